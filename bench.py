@@ -18,6 +18,16 @@ over xGMI via RCCL send/recv, then the decode group runs the timed region.
 Timed region: exactly K decode steps at full concurrency, bracketed by
 barrier + torch.cuda.synchronize on both sides; value = aggregate output
 tokens / elapsed (max over ranks).
+
+A plain N=1 (or --mode dp) run does only what that figure needs: it builds
+the engine, puts the requests straight into their decode state (seeded
+synthetic KV for the ISL tokens of context, see attach_at_decode), warms
+up, times the K steps and prints the result line. --full adds the
+supplementary measurements: the prompts are really prefilled, and
+ttft_p50_s / prefill_time_s in the result line's config (null in a plain
+run) are measured. N>1 disaggregated runs always prefill: the prefill group
+and the KV hand-off are what they exercise. --dump-outputs DIR saves what
+the last timed step returned (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -54,6 +64,14 @@ def parse_args():
     p.add_argument("--max-batched-tokens", type=int, default=0)
     p.add_argument("--moe-ep", action="store_true",
                    help="expert parallelism for MoE models (auto for N>1)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step returned as DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also take the supplementary measurements: really "
+                        "prefill the prompts and report TTFT and prefill "
+                        "time (a plain run only produces the headline "
+                        "decode figure)")
     return p.parse_args()
 
 
@@ -112,7 +130,8 @@ def emit(args, world, value, ms_per_step, ttft_p50, prefill_time, mode, conc):
             "kv_cache_dtype": args.kv_cache_dtype,
             "ttft_p50_s": round(ttft_p50, 3) if ttft_p50 else None,
             "itl_p50_ms": round(ms_per_step, 3),
-            "prefill_time_s": round(prefill_time, 2),
+            "prefill_time_s": (round(prefill_time, 2)
+                               if prefill_time is not None else None),
         },
     }
     print(json.dumps(result), flush=True)
@@ -123,7 +142,73 @@ def dev_sync(device):
         torch.cuda.synchronize()
 
 
+def dump_outputs(out_dir, eng, outs, req_ids):
+    """Write what the last timed step handed back, one row per request in
+    submission order (inputs and weights are seeded, so two builds can be
+    compared array for array):
+      tokens.npy  [n]    the step's new token per request (-1: none)
+      logits.npy  [n, V] the fp32 logits those tokens were sampled from
+                         (graph decode path only: its persistent buffer
+                         still holds the last step's rows)
+    """
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    tok = {so.req_id: so.new_token for so in outs}
+    tokens = np.array([-1 if tok.get(r) is None else tok[r] for r in req_ids],
+                      dtype=np.float32)
+    np.save(os.path.join(out_dir, "tokens.npy"), tokens)
+    gr = eng.graph_runner
+    # not dirty: the last step was a graph decode step of exactly gr.reqs
+    if gr is not None and not gr.dirty:
+        row = {r.req_id: i for i, r in enumerate(gr.reqs)}
+        order = [row[r] for r in req_ids if r in row]
+        logits = gr.logits[:len(gr.reqs)].float().cpu().numpy()[order]
+        max_cols = (48 << 20) // (4 * max(1, logits.shape[0]))
+        if logits.shape[1] > max_cols:
+            # large batch: a fixed, seeded sample of the vocabulary columns
+            cols = np.random.default_rng(0).choice(
+                logits.shape[1], max_cols, replace=False)
+            logits = logits[:, np.sort(cols)]
+        np.save(os.path.join(out_dir, "logits.npy"),
+                np.ascontiguousarray(logits, dtype=np.float32))
+
+
 # ---------------------------------------------------------------------------
+def attach_at_decode(eng, args, mc, req_ids, prompts, seed):
+    """Put every request where its prefill would have left it, without
+    running the prefill: pages for the whole prompt allocated and filled
+    with seeded N(0,1) KV, one (seeded) first output token. Decode steps
+    cost the same whatever the KV holds - they read ISL tokens of context
+    per sequence - so this is all the decode tok/s figure needs; the real
+    prefill with its TTFT runs under --full."""
+    from dynamo_amd.engine import SamplingParams
+    from dynamo_amd.engine.kv_cache import SequenceKV
+    rng = random.Random(seed)
+    used = []
+    for rid, prompt in zip(req_ids, prompts):
+        kv = SequenceKV(eng.alloc, eng.cfg.block_salt)
+        kv.ensure_capacity(len(prompt))
+        used += kv.pages
+        req = eng.add_request(rid, prompt, SamplingParams(
+            max_tokens=args.osl, temperature=0.0, ignore_eos=True))
+        req.kv = kv
+        req.num_computed = len(prompt)
+        req.output_tokens.append(rng.randrange(mc.vocab_size))
+    buf = eng.runner.kv_pool.buffer
+    gen = torch.Generator(device=buf.device)
+    gen.manual_seed(seed)
+    ids = torch.tensor(used, dtype=torch.long, device=buf.device)
+    for layer in range(buf.shape[0]):
+        for kv_plane in range(2):
+            fill = torch.randn((len(used),) + tuple(buf.shape[3:]),
+                               generator=gen, device=buf.device,
+                               dtype=torch.float32)
+            dst, src = buf[layer, kv_plane], fill.to(buf.dtype)
+            if buf.element_size() == 1:   # fp8 KV: scatter as raw bytes
+                dst, src = dst.view(torch.uint8), src.view(torch.uint8)
+            dst.index_copy_(0, ids, src)
+
+
 def run_single_or_dp(args, world, rank, local_rank, device):
     from dynamo_amd.engine import LLMEngine, SamplingParams
     from dynamo_amd.models.registry import resolve_model_config
@@ -138,21 +223,28 @@ def run_single_or_dp(args, world, rank, local_rank, device):
 
     conc = args.conc_per_gpu
     prompts = make_prompts(args, mc, conc, 1234 + rank)
-    submit_t = {}
+    req_ids = [f"r{rank}-{i}" for i in range(conc)]
     ttfts = []
-    for i, prompt in enumerate(prompts):
-        rid = f"r{rank}-{i}"
-        eng.add_request(rid, prompt, SamplingParams(
-            max_tokens=args.osl, temperature=0.0, ignore_eos=True))
-        submit_t[rid] = time.monotonic()
+    prefill_time = None
+    if args.full:
+        # supplementary: really prefill every prompt and record TTFT
+        submit_t = {}
+        for rid, prompt in zip(req_ids, prompts):
+            eng.add_request(rid, prompt, SamplingParams(
+                max_tokens=args.osl, temperature=0.0, ignore_eos=True))
+            submit_t[rid] = time.monotonic()
 
-    t_pre0 = time.monotonic()
-    while any(not r.output_tokens for r in eng.requests.values()):
-        for so in eng.step():
-            if so.num_output_tokens == 1:
-                ttfts.append(time.monotonic() - submit_t[so.req_id])
-    dev_sync(device)
-    prefill_time = time.monotonic() - t_pre0
+        t_pre0 = time.monotonic()
+        while any(not r.output_tokens for r in eng.requests.values()):
+            for so in eng.step():
+                if so.num_output_tokens == 1:
+                    ttfts.append(time.monotonic() - submit_t[so.req_id])
+        dev_sync(device)
+        prefill_time = time.monotonic() - t_pre0
+    else:
+        attach_at_decode(eng, args, mc, req_ids, prompts, 4321 + rank)
+        eng.step()   # admission: every request joins the running batch
+        dev_sync(device)
 
     for _ in range(args.warmup):
         eng.step()
@@ -161,10 +253,14 @@ def run_single_or_dp(args, world, rank, local_rank, device):
         dist.barrier()
     t0 = time.monotonic()
     gen = 0
+    outs = []
     for _ in range(args.steps):
-        gen += len(eng.step())
+        outs = eng.step()
+        gen += len(outs)
     dev_sync(device)
     elapsed = time.monotonic() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, outs, req_ids)
     if world > 1:
         dist.barrier()
         t = torch.tensor([elapsed, float(gen)])
@@ -410,12 +506,17 @@ def run_disagg(args, world, rank, local_rank, device):
         dist.barrier()
         t0 = time.monotonic()
         gen = 0
+        outs = []
         for _ in range(args.steps):
-            gen += len(side_cmd({"step": True}))
+            outs = side_cmd({"step": True})
+            gen += len(outs)
         side_cmd({"barrier": True})
         dev_sync(device)
         dist.barrier()
         elapsed = time.monotonic() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, eng, outs,
+                         [f"d{i}" for i in range(conc_total)])
         side_cmd({"shutdown": True})
         dist.send_object_list([{
             "value": gen / elapsed,

@@ -9,9 +9,22 @@ preprocessor.rs OpenAIPreprocessor; ours is the Python analog).
 """
 from __future__ import annotations
 
+import codecs
 from typing import List, Optional
 
 import jinja2
+
+_BYTE_ERRORS = "dynamo_amd_latin1"
+_Utf8Stream = codecs.getincrementaldecoder("utf-8")
+
+
+def _latin1_errors(exc):
+    if not isinstance(exc, UnicodeDecodeError):
+        raise exc
+    return exc.object[exc.start:exc.end].decode("latin-1"), exc.end
+
+
+codecs.register_error(_BYTE_ERRORS, _latin1_errors)
 
 DEFAULT_CHAT_TEMPLATE = (
     "{% for m in messages %}"
@@ -38,19 +51,20 @@ class ByteTokenizer:
         return ([self.bos_id] if add_bos else []) + ids
 
     def decode(self, ids: List[int]) -> str:
+        # Streaming-safe: the text of a prefix of `ids` is always a prefix
+        # of the text of `ids`, whatever bytes follow. Valid UTF-8 decodes
+        # as such; a byte that cannot be part of a valid sequence
+        # (synthetic tokens) maps to its latin-1 char, which keeps distinct
+        # bytes distinct (utf-8 replacement chars would collapse them); an
+        # incomplete sequence at the very end is held back until the bytes
+        # that complete or invalidate it arrive.
         bs = bytes(i for i in ids if 0 <= i < 256)
-        try:
-            return bs.decode("utf-8")
-        except UnicodeDecodeError:
-            # non-UTF-8 byte streams (synthetic tokens): latin-1 maps every
-            # byte to a DISTINCT char, keeping decode stable and reversible
-            # (utf-8 replacement chars collapse distinct bytes and break
-            # incremental/full decode consistency)
-            return bs.decode("latin-1")
+        return _Utf8Stream(_BYTE_ERRORS).decode(bs, False)
 
     def decode_incremental(self, ids: List[int], prev_len: int) -> str:
-        """Decode the new suffix, robust to split UTF-8 sequences."""
-        return self.decode(ids[prev_len:])
+        """Text added by ids[prev_len:], robust to split UTF-8 sequences:
+        concatenated chunks equal decode(ids) for any chunking."""
+        return self.decode(ids)[len(self.decode(ids[:prev_len])):]
 
 
 class HFTokenizer:

@@ -31,12 +31,32 @@ def run_bench(nproc, extra, timeout=280):
 
 @pytest.mark.timeout(300)
 def test_bench_single():
-    r = run_bench(1, [])
+    r = run_bench(1, ["--full"])   # TTFT is a --full measurement
     assert r["n_gpus"] == 1
     assert r["value"] > 0
     assert r["scaling"] == "weak"
     assert r["config"]["parallelism"] == "agg1"
     assert r["config"]["ttft_p50_s"] is not None
+
+
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's tokens as float32 .npy
+    (one per request), identical from run to run with the same arguments.
+    A plain run skips the prefill, so it reports no TTFT."""
+    import numpy as np
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    r = run_bench(1, ["--dump-outputs", a])
+    assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["config"]["ttft_p50_s"] is None
+    run_bench(1, ["--dump-outputs", b])
+    ta = np.load(os.path.join(a, "tokens.npy"))
+    tb = np.load(os.path.join(b, "tokens.npy"))
+    assert ta.dtype == np.float32 and ta.shape == (2,)
+    assert (ta >= 0).all() and (ta == np.round(ta)).all()
+    assert np.array_equal(ta, tb)
+    total = sum(os.path.getsize(os.path.join(a, f)) for f in os.listdir(a))
+    assert total <= 64 << 20
 
 
 @pytest.mark.timeout(300)

@@ -174,15 +174,19 @@ def test_file_discovery_lease(tmp_path):
     assert d.list("ns", "backend") == []
 
 
-def test_request_plane_unix_socket(tmp_path):
+def test_request_plane_unix_socket(tmp_path, monkeypatch):
     """UDS transport: the same codec/endpoints over a Unix domain socket."""
     import asyncio
 
     from dynamo_amd.runtime.request_plane import (RequestPlaneClient,
                                                   RequestPlaneServer)
 
+    # sun_path holds ~107 bytes and pytest's tmp_path can be deeper than
+    # that: bind by a relative name from inside the directory instead
+    monkeypatch.chdir(tmp_path)
+
     async def main():
-        server = RequestPlaneServer(host=f"unix:{tmp_path}/rp.sock")
+        server = RequestPlaneServer(host="unix:rp.sock")
 
         async def echo(payload, ctx):
             for i in range(3):
