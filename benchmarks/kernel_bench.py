@@ -100,6 +100,70 @@ def bench_sampling(B=16, V=128256):
     print(f"greedy       [B{B} V{V}]: {t*1e6:8.1f} us")
 
 
+def timeit_graph(fn, n=100, reps=20):
+    """Per-call time of a latency-bound kernel as the decode graph runs it:
+    n dependent calls captured into one hipGraph, so the figure is kernel +
+    dependent-kernel boundary without the eager host launch cost."""
+    fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(n):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    t0 = time.monotonic()
+    for _ in range(reps):
+        g.replay()
+    torch.cuda.synchronize()
+    return (time.monotonic() - t0) / (reps * n)
+
+
+def _fast_vs_general(name, fn):
+    """fn(allow_fast) -> one call; prints general | fast, alternated."""
+    ts = {False: [], True: []}
+    for _ in range(3):
+        for fast in (False, True):
+            ts[fast].append(timeit_graph(lambda: fn(fast)))
+    g, f = min(ts[False]), min(ts[True])
+    print(f"{name}: general {g*1e6:7.2f} us | fast {f*1e6:7.2f} us "
+          f"({g/f:4.2f}x)")
+
+
+def bench_rmsnorm_decode(rows=16, D=8192):
+    x = torch.randn(rows, D, dtype=torch.bfloat16, device="cuda")
+    res = torch.zeros(rows, D, dtype=torch.bfloat16, device="cuda")
+    w = torch.ones(D, dtype=torch.bfloat16, device="cuda")
+    _fast_vs_general(f"fused_add_rmsnorm [{rows}x{D}]",
+                     lambda fast: ops.fused_add_rmsnorm(x, res, w, 1e-5, fast))
+    _fast_vs_general(f"rmsnorm           [{rows}x{D}]",
+                     lambda fast: ops.rmsnorm(x, w, 1e-5, fast))
+
+
+def bench_rope_append(T=16, Hq=64, Hkv=8, ps=64):
+    hd = 128
+    npages = (T + ps - 1) // ps
+    qkv = torch.randn(T, (Hq + 2 * Hkv) * hd, dtype=torch.bfloat16,
+                      device="cuda")
+    kc = torch.zeros(npages, Hkv, ps, hd, dtype=torch.bfloat16, device="cuda")
+    vc = torch.zeros(npages, Hkv, hd, ps, dtype=torch.bfloat16, device="cuda")
+    pos = torch.arange(T, dtype=torch.int32, device="cuda")
+    slots = torch.arange(T, dtype=torch.int64, device="cuda")
+    cs = ops.make_cos_sin_cache(max(T, 64), hd, 10000.0, device="cuda")
+    q_out = torch.empty(T, Hq * hd, dtype=torch.bfloat16, device="cuda")
+    _fast_vs_general(
+        f"rope_append  [T{T} Hq{Hq}/{Hkv} vt1]",
+        lambda fast: ops.hip().rope_append_qkv(q_out, kc, vc, qkv, None, pos,
+                                               slots, cs, True, fast))
+
+
+def bench_sampling_decode(B=16, V=128256):
+    logits = torch.randn(B, V, device="cuda")
+    out = torch.empty(B, dtype=torch.int32, device="cuda")
+    _fast_vs_general(f"greedy       [B{B} V{V}]",
+                     lambda fast: ops.hip().greedy_sample(out, logits, fast))
+
+
 def bench_gemm(M=16, K=8192, N=8192):
     a = torch.randn(M, K, dtype=torch.bfloat16, device="cuda")
     w = torch.randn(N, K, dtype=torch.bfloat16, device="cuda")
@@ -135,6 +199,13 @@ if __name__ == "__main__":
         bench_kv_append()
     if w in ("all", "sample"):
         bench_sampling()
+    if w in ("all", "tail"):
+        # the decode step's latency-bound kernels at the flagship shapes,
+        # plus rope-append at the prefill shape
+        bench_rmsnorm_decode()
+        bench_rope_append()
+        bench_rope_append(T=8192)
+        bench_sampling_decode()
     if w in ("all", "gemm"):
         bench_gemm()
         bench_gemm(M=8192)

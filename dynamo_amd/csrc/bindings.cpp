@@ -5,15 +5,17 @@
 namespace py = pybind11;
 
 // norm.hip
-void rmsnorm(torch::Tensor out, torch::Tensor input, torch::Tensor weight, double eps);
+void rmsnorm(torch::Tensor out, torch::Tensor input, torch::Tensor weight,
+             double eps, bool allow_fast);
 void fused_add_rmsnorm(torch::Tensor input, torch::Tensor residual,
-                       torch::Tensor weight, double eps);
+                       torch::Tensor weight, double eps, bool allow_fast);
 // rope.hip
 void rope_append_qkv(torch::Tensor q_out, torch::Tensor kcache,
                      torch::Tensor vcache, torch::Tensor qkv,
                      c10::optional<torch::Tensor> bias,
                      torch::Tensor positions, torch::Tensor slot_mapping,
-                     torch::Tensor cos_sin_cache, bool v_transposed);
+                     torch::Tensor cos_sin_cache, bool v_transposed,
+                     bool allow_fast);
 void rope_inplace(torch::Tensor q, torch::Tensor k, torch::Tensor positions,
                   torch::Tensor cos_sin_cache, int64_t num_q_heads,
                   int64_t num_k_heads, int64_t head_dim);
@@ -44,13 +46,14 @@ void attention_prefill_paged(torch::Tensor out, torch::Tensor q,
                              torch::Tensor seq_q_len, torch::Tensor seq_ctx_len,
                              double scale, bool v_transposed);
 // sampling.hip
-void greedy_sample(torch::Tensor out, torch::Tensor logits);
+void greedy_sample(torch::Tensor out, torch::Tensor logits, bool allow_fast);
 void topkp_sample(torch::Tensor out, torch::Tensor logits,
                   torch::Tensor inv_temp, torch::Tensor top_k,
                   torch::Tensor top_p, int64_t seed,
                   c10::optional<torch::Tensor> row_seeds);
 void gumbel_sample(torch::Tensor out, torch::Tensor logits, torch::Tensor inv_temp,
-                   int64_t seed, c10::optional<torch::Tensor> row_seeds);
+                   int64_t seed, c10::optional<torch::Tensor> row_seeds,
+                   bool allow_fast);
 // moe.hip
 void moe_grouped_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                       torch::Tensor tiles);
@@ -70,14 +73,19 @@ torch::Tensor pv_probe(int64_t hot);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "dynamo_amd native MI355X (gfx950) kernels";
-  m.def("rmsnorm", &rmsnorm);
-  m.def("fused_add_rmsnorm", &fused_add_rmsnorm);
+  // allow_fast = false keeps an op on its general kernel, so a test can
+  // compare the two paths on the same inputs in one process
+  m.def("rmsnorm", &rmsnorm, py::arg("out"), py::arg("input"),
+        py::arg("weight"), py::arg("eps"), py::arg("allow_fast") = true);
+  m.def("fused_add_rmsnorm", &fused_add_rmsnorm, py::arg("input"),
+        py::arg("residual"), py::arg("weight"), py::arg("eps"),
+        py::arg("allow_fast") = true);
   m.def("rope_inplace", &rope_inplace);
   m.def("rope_append_qkv", &rope_append_qkv,
         py::arg("q_out"), py::arg("kcache"), py::arg("vcache"),
         py::arg("qkv"), py::arg("bias"), py::arg("positions"),
         py::arg("slot_mapping"), py::arg("cos_sin"),
-        py::arg("v_transposed") = false);
+        py::arg("v_transposed") = false, py::arg("allow_fast") = true);
   m.def("silu_mul", &silu_mul);
   m.def("gelu", &gelu);
   m.def("kv_cache_append", &kv_cache_append, py::arg("kcache"),
@@ -99,10 +107,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("page_table"), py::arg("tile_seq"), py::arg("tile_q0"),
         py::arg("seq_q_start"), py::arg("seq_q_len"), py::arg("seq_ctx_len"),
         py::arg("scale"), py::arg("v_transposed") = false);
-  m.def("greedy_sample", &greedy_sample);
+  m.def("greedy_sample", &greedy_sample, py::arg("out"), py::arg("logits"),
+        py::arg("allow_fast") = true);
   m.def("gumbel_sample", &gumbel_sample, py::arg("out"), py::arg("logits"),
         py::arg("inv_temp"), py::arg("seed"),
-        py::arg("row_seeds") = py::none());
+        py::arg("row_seeds") = py::none(), py::arg("allow_fast") = true);
   m.def("topkp_sample", &topkp_sample, py::arg("out"), py::arg("logits"),
         py::arg("inv_temp"), py::arg("top_k"), py::arg("top_p"),
         py::arg("seed"), py::arg("row_seeds") = py::none());

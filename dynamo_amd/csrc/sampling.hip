@@ -15,6 +15,7 @@
 namespace {
 
 constexpr int kBlock = 512;
+constexpr int kScanUnroll = 8;  // 16-byte loads in flight per thread
 
 DEVINL uint64_t hash_u64(uint64_t x) {
   // splitmix64 finalizer
@@ -24,13 +25,34 @@ DEVINL uint64_t hash_u64(uint64_t x) {
   return x ^ (x >> 31);
 }
 
+// One candidate of the argmax scan. The winner rule (strictly greater, or
+// equal with the lower index) is a total order on (score, index), so the
+// result does not depend on the order in which candidates are scanned.
 template <bool GUMBEL>
-__global__ void sample_kernel(int32_t* __restrict__ out,          // [B]
-                              const float* __restrict__ logits,   // [B, V]
-                              const float* __restrict__ inv_temp, // [B] or null
-                              uint64_t seed,
-                              const uint64_t* __restrict__ row_seeds,  // [B] or null
-                              int V) {
+DEVINL void sample_consider(float logit, int v, float it, uint64_t rs,
+                            float& best, int& besti) {
+  float x = logit * it;
+  if constexpr (GUMBEL) {
+    const uint64_t h = hash_u64(rs ^ (uint64_t)v);
+    // uniform in (0,1): use top 53 bits
+    const float u = (float)((h >> 11) + 1) * 4.8828125e-4f * 2.2737367544323206e-13f;
+    x += -__logf(-__logf(u));
+  }
+  if (x > best || (x == best && v < besti)) { best = x; besti = v; }
+}
+
+// FAST: the row is read as 16-byte vectors, kScanUnroll loads in flight per
+// thread, with a scalar head up to the first 16-byte boundary (rows of a
+// V % 4 != 0 matrix start unaligned) and a scalar tail. !FAST: one scalar
+// load per iteration.
+template <bool GUMBEL, bool FAST>
+__global__ __launch_bounds__(kBlock) void sample_kernel(
+    int32_t* __restrict__ out,          // [B]
+    const float* __restrict__ logits,   // [B, V]
+    const float* __restrict__ inv_temp, // [B] or null
+    uint64_t seed,
+    const uint64_t* __restrict__ row_seeds,  // [B] or null
+    int V) {
   const int b = blockIdx.x;
   const float* row = logits + (int64_t)b * V;
   const float it = GUMBEL ? inv_temp[b] : 1.f;
@@ -40,15 +62,38 @@ __global__ void sample_kernel(int32_t* __restrict__ out,          // [B]
 
   float best = -1e38f;
   int besti = -1;
-  for (int v = threadIdx.x; v < V; v += kBlock) {
-    float x = row[v] * it;
-    if constexpr (GUMBEL) {
-      const uint64_t h = hash_u64(rs ^ (uint64_t)v);
-      // uniform in (0,1): use top 53 bits
-      const float u = (float)((h >> 11) + 1) * 4.8828125e-4f * 2.2737367544323206e-13f;
-      x += -__logf(-__logf(u));
+  if constexpr (FAST) {
+    const int mis = (int)((reinterpret_cast<uintptr_t>(row) >> 2) & 3);
+    const int head = min(V, (4 - mis) & 3);
+    const int n4 = (V - head) / 4;
+    const float4v* row4 = reinterpret_cast<const float4v*>(row + head);
+    for (int i0 = 0; i0 < n4; i0 += kScanUnroll * kBlock) {
+      float4v r[kScanUnroll];
+#pragma unroll
+      for (int u = 0; u < kScanUnroll; u++) {
+        const int i = i0 + u * kBlock + threadIdx.x;
+        if (i < n4) r[u] = row4[i];
+      }
+#pragma unroll
+      for (int u = 0; u < kScanUnroll; u++) {
+        const int i = i0 + u * kBlock + threadIdx.x;
+        if (i < n4) {
+#pragma unroll
+          for (int e = 0; e < 4; e++)
+            sample_consider<GUMBEL>(r[u][e], head + i * 4 + e, it, rs, best,
+                                    besti);
+        }
+      }
     }
-    if (x > best || (x == best && v < besti)) { best = x; besti = v; }
+    // scalar head and tail: at most 3 elements each
+    if ((int)threadIdx.x < head)
+      sample_consider<GUMBEL>(row[threadIdx.x], threadIdx.x, it, rs, best,
+                              besti);
+    const int v = head + n4 * 4 + threadIdx.x;
+    if (v < V) sample_consider<GUMBEL>(row[v], v, it, rs, best, besti);
+  } else {
+    for (int v = threadIdx.x; v < V; v += kBlock)
+      sample_consider<GUMBEL>(row[v], v, it, rs, best, besti);
   }
   // wave reduce (value, index)
 #pragma unroll
@@ -199,16 +244,18 @@ __global__ __launch_bounds__(kBlock) void topkp_sample_kernel(
 
 }  // namespace
 
-void greedy_sample(torch::Tensor out, torch::Tensor logits) {
+void greedy_sample(torch::Tensor out, torch::Tensor logits, bool allow_fast) {
   TORCH_CHECK(logits.is_cuda() && logits.dtype() == torch::kFloat32);
   TORCH_CHECK(out.dtype() == torch::kInt32);
   const int B = logits.size(0);
   const int V = logits.size(1);
   if (B == 0) return;
   auto stream = at::cuda::getCurrentHIPStream();
-  sample_kernel<false><<<B, kBlock, 0, stream>>>(
-      out.data_ptr<int32_t>(), logits.data_ptr<float>(), nullptr, 0, nullptr,
-      V);
+  auto kern = allow_fast ? sample_kernel<false, true>
+                         : sample_kernel<false, false>;
+  kern<<<B, kBlock, 0, stream>>>(out.data_ptr<int32_t>(),
+                                 logits.data_ptr<float>(), nullptr, 0, nullptr,
+                                 V);
   HIP_CHECK_KERNEL();
 }
 
@@ -221,14 +268,17 @@ static const uint64_t* opt_seeds(const c10::optional<torch::Tensor>& t,
 }
 
 void gumbel_sample(torch::Tensor out, torch::Tensor logits, torch::Tensor inv_temp,
-                   int64_t seed, c10::optional<torch::Tensor> row_seeds) {
+                   int64_t seed, c10::optional<torch::Tensor> row_seeds,
+                   bool allow_fast) {
   TORCH_CHECK(logits.is_cuda() && logits.dtype() == torch::kFloat32);
   TORCH_CHECK(inv_temp.dtype() == torch::kFloat32);
   const int B = logits.size(0);
   const int V = logits.size(1);
   if (B == 0) return;
   auto stream = at::cuda::getCurrentHIPStream();
-  sample_kernel<true><<<B, kBlock, 0, stream>>>(
+  auto kern = allow_fast ? sample_kernel<true, true>
+                         : sample_kernel<true, false>;
+  kern<<<B, kBlock, 0, stream>>>(
       out.data_ptr<int32_t>(), logits.data_ptr<float>(),
       inv_temp.data_ptr<float>(), (uint64_t)seed, opt_seeds(row_seeds, B), V);
   HIP_CHECK_KERNEL();

@@ -41,18 +41,19 @@ def hip_available() -> bool:
 
 
 # --------------------------------------------------------------------------
-def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Tensor:
+def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float,
+            allow_fast: bool = True) -> torch.Tensor:
     if x.is_cuda:
         out = torch.empty_like(x)
-        hip().rmsnorm(out, x.contiguous(), weight, eps)
+        hip().rmsnorm(out, x.contiguous(), weight, eps, allow_fast)
         return out
     return torch_ref.rmsnorm(x, weight, eps)
 
 
-def fused_add_rmsnorm(x, residual, weight, eps):
+def fused_add_rmsnorm(x, residual, weight, eps, allow_fast=True):
     """residual <- x + residual (in place); returns normalized residual."""
     if x.is_cuda:
-        hip().fused_add_rmsnorm(x, residual, weight, eps)
+        hip().fused_add_rmsnorm(x, residual, weight, eps, allow_fast)
         return x
     return torch_ref.fused_add_rmsnorm(x, residual, weight, eps)
 
@@ -96,7 +97,7 @@ def kv_cache_append(kcache, vcache, k, v, slot_mapping,
 
 def rope_append_qkv(qkv, bias, positions, slot_mapping, cos_sin,
                     kcache, vcache, num_q_heads, num_kv_heads, head_dim,
-                    v_transposed=False):
+                    v_transposed=False, allow_fast=True):
     """Fused QKV epilogue: strided qkv read (+bias) -> rope(q,k) ->
     q contiguous out, k/v scattered into the paged cache. One kernel
     instead of {q copy, k copy, rope, kv_append}. Returns q [T, Hq*hd]."""
@@ -105,7 +106,7 @@ def rope_append_qkv(qkv, bias, positions, slot_mapping, cos_sin,
         q_out = torch.empty(T, num_q_heads * head_dim, dtype=qkv.dtype,
                             device=qkv.device)
         hip().rope_append_qkv(q_out, kcache, vcache, qkv, bias, positions,
-                              slot_mapping, cos_sin, v_transposed)
+                              slot_mapping, cos_sin, v_transposed, allow_fast)
         return q_out
     # CPU reference: the unfused sequence
     if bias is not None:
@@ -206,11 +207,11 @@ def attention_prefill_paged(q, kcache, vcache, page_table, seq_q_start,
                                              v_transposed=v_transposed)
 
 
-def greedy_sample(logits: torch.Tensor) -> torch.Tensor:
+def greedy_sample(logits: torch.Tensor, allow_fast: bool = True) -> torch.Tensor:
     if logits.is_cuda:
         out = torch.empty(logits.shape[0], dtype=torch.int32,
                           device=logits.device)
-        hip().greedy_sample(out, logits.float().contiguous())
+        hip().greedy_sample(out, logits.float().contiguous(), allow_fast)
         return out
     return torch_ref.greedy_sample(logits)
 
@@ -228,12 +229,13 @@ def _splitmix64(x: torch.Tensor) -> torch.Tensor:
 
 
 def gumbel_sample(logits: torch.Tensor, inv_temp: torch.Tensor,
-                  seed: int, row_seeds: torch.Tensor = None) -> torch.Tensor:
+                  seed: int, row_seeds: torch.Tensor = None,
+                  allow_fast: bool = True) -> torch.Tensor:
     if logits.is_cuda:
         out = torch.empty(logits.shape[0], dtype=torch.int32,
                           device=logits.device)
         hip().gumbel_sample(out, logits.float().contiguous(), inv_temp, seed,
-                            row_seeds)
+                            row_seeds, allow_fast)
         return out
     # CPU: DETERMINISTIC counter-based Gumbel noise — the same
     # splitmix64(row_seed ^ v) stream as the HIP kernel (row_seed defaults
