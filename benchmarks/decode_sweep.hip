@@ -101,7 +101,7 @@ static Bufs make(int G) {
 // swapped-operand MFMA variant: bench + elementwise compare vs the proven
 // paged_decode_mfma output
 template <int G, int DEFER = 1, int PRIO = 1, int KPF = 0, int VS = 80, int XK2 = 0,
-          int VT = 0, int LG2 = 0, int MINW = 1>
+          int VT = 0, int LG2 = 0, int MINW = 1, int NTKV = 0>
 static void run_mfma_swapped(const Bufs& bf, bool check) {
   dim3 grid(B, Hkv, bf.C);
   // VT4/5 stage K (and V) through the per-wave v_lds region; VT1-3 skip
@@ -112,10 +112,10 @@ static void run_mfma_swapped(const Bufs& bf, bool check) {
   const int iters = 30;
   if (lds > 65536)
     (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&paged_decode_mfma_swapped<DEFER, PRIO, KPF, 0, VS, XK2, VT, LG2, MINW>),
+        reinterpret_cast<const void*>(&paged_decode_mfma_swapped<DEFER, PRIO, KPF, 0, VS, XK2, VT, LG2, MINW, NTKV>),
         hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   auto launch = [&] {
-    paged_decode_mfma_swapped<DEFER, PRIO, KPF, 0, VS, XK2, VT, LG2, MINW><<<grid, kBlock, lds>>>(
+    paged_decode_mfma_swapped<DEFER, PRIO, KPF, 0, VS, XK2, VT, LG2, MINW, NTKV><<<grid, kBlock, lds>>>(
         bf.partial, bf.ml, bf.out, bf.q, bf.kc, VT ? bf.vct : bf.vc, bf.pt, bf.ctx,
         0.0883883f, kChunk, G, B, Hkv, bf.C, CTX / PS, 6, HD, nullptr);
     paged_decode_phase2<<<dim3(B, G * Hkv), 128>>>(
@@ -168,8 +168,8 @@ static void run_mfma_swapped(const Bufs& bf, bool check) {
   CK(hipEventElapsedTime(&ms, e0, e1));
   double t = ms / 1000.0 / iters;
   double gb = 2.0 * B * CTX * Hkv * HD * 2 / 1e9;
-  printf("G%d MFMA_SW DF%d PR%d KP%d VS%d X%d VT%d L%d W%d %8.1f us  %7.0f GB/s\n", G,
-         DEFER, PRIO, KPF, VS, XK2, VT, LG2, MINW, t * 1e6, gb / t);
+  printf("G%d MFMA_SW DF%d PR%d KP%d VS%d X%d VT%d L%d W%d NT%d %8.1f us  %7.0f GB/s\n", G,
+         DEFER, PRIO, KPF, VS, XK2, VT, LG2, MINW, NTKV, t * 1e6, gb / t);
   fflush(stdout);
 }
 
@@ -259,6 +259,11 @@ int main() {
     run_mfma_swapped<8, 1, 1, 0, 72, 0, 3, 0, 2>(bf, false);  // VT3 minw2
     run_mfma_swapped<8, 0, 0, 0, 72, 0, 4, 0, 1>(bf, true);   // VT4 chk
     run_mfma_swapped<8, 1, 1, 0, 72, 0, 4, 0, 1>(bf, false);  // VT4
+    // VT4 with non-temporal K/V loads (production switch DYNAMO_DECODE_NT);
+    // K + V are 537 MB here, so the replay loop is already cache-cold
+    run_mfma_swapped<8, 0, 0, 0, 72, 0, 4, 0, 1, 1>(bf, true);   // VT4 nt chk
+    run_mfma_swapped<8, 1, 1, 0, 72, 0, 4, 0, 1, 1>(bf, false);  // VT4 nt
+    run_mfma_swapped<8, 1, 1, 0, 72, 0, 4, 0, 1>(bf, false);     // VT4 again
     run_mfma_swapped<8, 0, 0, 0, 72, 0, 5, 0, 1>(bf, true);   // VT5 chk
     run_mfma_swapped<8, 1, 1, 0, 72, 0, 5, 0, 1>(bf, false);  // VT5
     run_mfma_swapped<8, 1, 1, 0, 72, 0, 5, 0, 2>(bf, false);  // VT5 minw2

@@ -56,6 +56,18 @@ def bench_decode_attn(B=16, ctx=8192, Hq=64, Hkv=8, ps=64):
     gb = 2 * B * ctx * Hkv * hd * 2 / 1e9  # K+V bytes
     print(f"decode_attn  [B{B} ctx{ctx} Hq{Hq}/{Hkv}]: {t*1e6:8.1f} us  "
           f"{gb/t:7.2f} GB/s | vt {tv*1e6:8.1f} us {gb/tv:7.2f} GB/s")
+    # K/V cache policy of the d-major kernel (DYNAMO_DECODE_NT), alternated.
+    # K + V of one layer (537 MB at the flagship shape) exceed the Infinity
+    # Cache, so this replay loop is already cache-cold for them.
+    ts = {0: [], 1: []}
+    for _ in range(3):
+        for nt in (0, 1):
+            ts[nt].append(timeit(lambda: ops.paged_attention_decode(
+                q, kc, vct, pt, ctxl, hd ** -0.5, scratch, v_transposed=True,
+                nt_policy=nt)))
+    d, n = min(ts[0]), min(ts[1])
+    print(f"  vt K/V policy: default {d*1e6:8.1f} us {gb/d:7.2f} GB/s | "
+          f"nt {n*1e6:8.1f} us {gb/n:7.2f} GB/s")
 
 
 def bench_prefill_attn(S=8192, Hq=32, Hkv=8, ps=64, v_transposed=False):
@@ -174,6 +186,52 @@ def bench_gemm(M=16, K=8192, N=8192):
           f"{gb/t:7.2f} GB/s")
 
 
+def bench_skinny_gemm(M=16):
+    """Decode weight GEMMs at the flagship shapes, cache-cold: launch i reads
+    copy i % R of W, R * bytes(W) >= 1 GiB (the step never re-reads a matrix
+    before 137 GB of other weights have passed). hipBLASLt under the
+    project's TunableOp table vs the in-tree kernel at the shape's shipped
+    configuration (row-coalesced WPB8/U1/NT2 where the shape is not shipped),
+    with non-temporal and with default-policy W loads."""
+    from dynamo_amd.utils import enable_tunableop
+    enable_tunableop(tuning=False)
+    x_by_k = {}
+    for name, N, K in (("qkv", 10240, 8192), ("o", 8192, 8192),
+                       ("gateup", 57344, 8192), ("down", 8192, 28672),
+                       ("lm_head", 128256, 8192)):
+        x = x_by_k.setdefault(K, torch.randn(M, K, dtype=torch.bfloat16,
+                                             device="cuda"))
+        wbytes = N * K * 2
+        R = max(2, -(-(1 << 30) // wbytes))
+        ws = [torch.randn(N, K, dtype=torch.bfloat16, device="cuda") * 0.02
+              for _ in range(R)]
+        y = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
+        cfg = ops.SKINNY_GEMM_SHAPES.get((N, K), (8, 1, 2, True, True))
+        i = [0]
+
+        def lib():
+            i[0] += 1
+            return torch.nn.functional.linear(x, ws[i[0] % R])
+
+        def ours(nontemporal=True):
+            i[0] += 1
+            ops.hip().skinny_gemm(y, x, ws[i[0] % R], *cfg[:3], nontemporal,
+                                  cfg[4])
+
+        ts = {"lib": [], "nt": [], "dflt": []}
+        for _ in range(3):
+            ts["lib"].append(timeit(lib, iters=24))
+            ts["nt"].append(timeit(ours, iters=24))
+            ts["dflt"].append(timeit(lambda: ours(False), iters=24))
+        gb = wbytes / 1e9
+        row = " | ".join(f"{k} {min(v)*1e6:7.1f} us {gb/min(v)/1e3:5.2f} TB/s"
+                         for k, v in ts.items())
+        shipped = "shipped" if (N, K) in ops.SKINNY_GEMM_SHAPES else "library"
+        print(f"gemm cold {name:8s}[{M}x{K}x{N}] R={R} w{cfg[0]}u{cfg[1]}"
+              f"n{cfg[2]} ({shipped}): {row}")
+        del ws
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--which", default="all")
@@ -209,3 +267,4 @@ if __name__ == "__main__":
     if w in ("all", "gemm"):
         bench_gemm()
         bench_gemm(M=8192)
+        bench_skinny_gemm()

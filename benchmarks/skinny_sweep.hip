@@ -1,11 +1,17 @@
 // Skinny-M (decode-regime) GEMM sweep for MI355X/gfx950.
 //
 // y[M<=16, N] = x[M, K] @ W[N, K]^T, bf16 in / bf16 out, fp32 accum.
-// At decode M=conc (16): the GEMM is pure W-streaming. hipBLASLt measures
-// 5.3-5.9 TB/s on the flagship shapes (benchmarks/gemm_probe.py); HBM3E
-// streaming peak is ~7 TB/s, so a dedicated kernel has ~15-25% headroom.
+// At decode M=conc (16): the GEMM is pure W-streaming. In the decode step
+// every W byte is read once per step (137 GB of weights pass between two
+// uses of a matrix), so the rate that matters is the COLD one: each timed
+// launch rotates over R distinct copies of W with R * bytes(W) >= 1 GiB and
+// never touches the buffer of the launch before it. The same-buffer ("hot")
+// rate is printed next to it; for the o / qkv shapes (134 / 168 MB) it is an
+// Infinity-Cache figure the step never sees. The hipBLASLt baseline in the
+// same two cache states is benchmarks/gemm_probe.py.
 //
-// Design (see dynamo_amd/csrc/skinny_gemm.hip for the production copy):
+// Design (the kernel is dynamo_amd/csrc/skinny_gemm_impl.h, shared with the
+// production binding dynamo_amd/csrc/skinny_gemm.hip):
 //   mfma_f32_16x16x32_bf16 with A = x, B = W^T. Per-lane operand layout
 //   (lr = lane&15, lg = lane>>4):
 //     A-frag: x[lr][k0 + lg*8 .. +8]        -> one b128 load, contiguous K
@@ -14,6 +20,14 @@
 //   staging, no transpose, no swizzle. Each wave owns one (or NT) 16-col
 //   N-tiles and a K/WPB slice; the WPB waves of a block LDS-reduce their
 //   fp32 accumulators and wave 0 writes bf16.
+//
+// "COAL" rows are skinny_gemm_coal_kernel, the row-coalesced variant that
+// production runs (8 rows x 128 B per load + ds_bpermute; its U counts 64-k
+// double steps). The LDS-staged, persistent and ceiling kernels below are the
+// round-2 experiments, same-buffer only.
+//
+// Each (WPB, U, NT) point runs with default-policy W loads ("d") and with
+// non-temporal ones ("nt"); x is always on the default policy.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I dynamo_amd/csrc \
 //          benchmarks/skinny_sweep.hip -o benchmarks/skinny_sweep
@@ -24,106 +38,9 @@
 #include <cmath>
 #include <vector>
 
-#include "common.h"
+#include "skinny_gemm_impl.h"
 
-typedef __attribute__((ext_vector_type(4))) unsigned uint4v;
-
-// One wave per (n-tile group, k-slice); WPB waves per block share an n-tile
-// group and split K. U = software pipeline unroll (loads for U steps in
-// flight). NT = n-tiles (16 cols each) per wave.
-template <int WPB, int U, int NT>
-__global__ __launch_bounds__(WPB * 64) void skinny_gemm_kernel(
-    const short* __restrict__ x,   // [M, K] bf16 row-major
-    const short* __restrict__ w,   // [N, K] bf16 row-major
-    short* __restrict__ y,         // [M, N] bf16 row-major
-    int M, int N, int K) {
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;       // 0..WPB-1 = k-slice
-  const int lr = lane & 15;
-  const int lg = lane >> 4;
-  const int n0 = (blockIdx.x * NT) * 16;  // first col of this block's tiles
-  if (n0 >= N) return;
-
-  const int kw = K / WPB;                 // K per wave (K % (WPB*32*U) == 0)
-  const int k0 = wid * kw;
-  const int steps = kw / 32;
-
-  // A source row: clamp to row 0 when M < 16 (those results are dropped).
-  const int ar = lr < M ? lr : 0;
-  const short* xp = x + (size_t)ar * K + k0 + lg * 8;
-  const short* wp[NT];
-#pragma unroll
-  for (int t = 0; t < NT; t++) {
-    const int col = n0 + t * 16 + lr;
-    wp[t] = w + (size_t)(col < N ? col : N - 1) * K + k0 + lg * 8;
-  }
-
-  f32x4 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; t++) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  bf16x8 abuf[U];
-  bf16x8 bbuf[NT][U];
-#pragma unroll
-  for (int u = 0; u < U; u++) {
-    abuf[u] = *reinterpret_cast<const bf16x8*>(xp + u * 32);
-#pragma unroll
-    for (int t = 0; t < NT; t++)
-      bbuf[t][u] = *reinterpret_cast<const bf16x8*>(wp[t] + u * 32);
-  }
-
-  for (int s = U; s < steps; s += U) {
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      bf16x8 a = abuf[u];
-      abuf[u] = *reinterpret_cast<const bf16x8*>(xp + (s + u) * 32);
-#pragma unroll
-      for (int t = 0; t < NT; t++) {
-        bf16x8 b = bbuf[t][u];
-        bbuf[t][u] = *reinterpret_cast<const bf16x8*>(wp[t] + (s + u) * 32);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[t], 0, 0, 0);
-      }
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < U; u++)
-#pragma unroll
-    for (int t = 0; t < NT; t++)
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(abuf[u], bbuf[t][u],
-                                                       acc[t], 0, 0, 0);
-
-  // Cross-wave reduction: waves 1..WPB-1 park their accumulators in LDS,
-  // wave 0 sums and writes bf16.
-  __shared__ f32x4 red[WPB > 1 ? (WPB - 1) * NT * 64 : 1];
-  if (WPB > 1) {
-    if (wid > 0) {
-#pragma unroll
-      for (int t = 0; t < NT; t++)
-        red[((wid - 1) * NT + t) * 64 + lane] = acc[t];
-    }
-    __syncthreads();
-    if (wid > 0) return;
-#pragma unroll
-    for (int t = 0; t < NT; t++)
-#pragma unroll
-      for (int r = 0; r < WPB - 1; r++) {
-        f32x4 o = red[(r * NT + t) * 64 + lane];
-        acc[t].x += o.x; acc[t].y += o.y; acc[t].z += o.z; acc[t].w += o.w;
-      }
-  }
-  // C layout: lane holds y[lg*4 + i][tilecol + lr], i = 0..3.
-#pragma unroll
-  for (int t = 0; t < NT; t++) {
-    const int col = n0 + t * 16 + lr;
-    if (col >= N) break;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int row = lg * 4 + i;
-      if (row < M)
-        y[(size_t)row * N + col] = f32_to_bf16(acc[t][i]);
-    }
-  }
-}
+using skinny::skinny_gemm_kernel;  // the register-streaming kernel
 
 // LDS-staged skinny GEMM: one 16-col n-tile per block, 4 waves. W tiles
 // (16 rows x KC cols) are staged cooperatively with fully-linear 1KB
@@ -421,15 +338,19 @@ __global__ __launch_bounds__(256) void stream_ceiling_kernel(
 static double bench(void (*kern)(const short*, const short*, short*, int, int,
                                  int),
                     int grid, int block, const short* x, const short* w,
-                    short* y, int M, int N, int K, int iters) {
+                    short* y, int M, int N, int K, int iters, int R = 1) {
+  // launch i reads W copy i % R (copies are N*K elements apart)
+  const size_t stride = (size_t)N * K;
   for (int i = 0; i < 5; i++)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, 0, x, w, y, M, N, K);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, 0, x,
+                       w + (i % R) * stride, y, M, N, K);
   hipEvent_t a, b;
   hipEventCreate(&a);
   hipEventCreate(&b);
   hipEventRecord(a);
   for (int i = 0; i < iters; i++)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, 0, x, w, y, M, N, K);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, 0, x,
+                       w + ((i + 5) % R) * stride, y, M, N, K);
   hipEventRecord(b);
   hipEventSynchronize(b);
   float ms;
@@ -469,6 +390,8 @@ int main(int argc, char** argv) {
   hipMalloc(&x, hx.size() * 2);
   // big W: replicate the host block (content irrelevant for timing; the
   // first 64 MB is real for numerics checks)
+  // (also the pool for the cold rotation: the largest need is 2 lm_head
+  // copies = 4.2 GB)
   size_t welems = (size_t)maxN * maxK;
   hipMalloc(&w, welems * 2);
   for (size_t off = 0; off < welems; off += hw.size()) {
@@ -488,7 +411,7 @@ int main(int argc, char** argv) {
     short* xd2;
     hipMalloc(&xd2, cx.size() * 2);
     hipMemcpy(xd2, cx.data(), cx.size() * 2, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL((skinny_gemm_kernel<4, 4, 1>), dim3(cN / 16),
+    hipLaunchKernelGGL((skinny_gemm_kernel<4, 4, 2, 1>), dim3(cN / 32),
                        dim3(256), 0, 0, xd2, w, y, M, cN, cK);
     hipMemcpy(hy.data(), y, hy.size() * 2, hipMemcpyDeviceToHost);
     double maxerr = 0;
@@ -501,7 +424,7 @@ int main(int argc, char** argv) {
         double err = std::abs(got - ref) / std::max(1.0, std::abs(ref));
         maxerr = std::max(maxerr, err);
       }
-    printf("numerics (K=%d N=%d WPB4 U4 NT1): maxrelerr=%.4f %s\n", cK, cN,
+    printf("numerics (K=%d N=%d WPB4 U4 NT2 nt): maxrelerr=%.4f %s\n", cK, cN,
            maxerr, maxerr < 0.02 ? "PASS" : "FAIL");
     hipLaunchKernelGGL((skinny_gemm_lds_kernel<512>), dim3(cN / 16),
                        dim3(256), 0, 0, xd2, w, y, M, cN, cK);
@@ -516,6 +439,19 @@ int main(int argc, char** argv) {
         double err = std::abs(got - ref) / std::max(1.0, std::abs(ref));
         maxerr = std::max(maxerr, err);
       }
+    {
+      // the row-coalesced variant must reproduce skinny_gemm_kernel bit for
+      // bit at equal WPB
+      std::vector<short> h0(M * cN), h1(M * cN);
+      hipLaunchKernelGGL((skinny_gemm_kernel<4, 4, 2, 0>), dim3(cN / 32),
+                         dim3(256), 0, 0, xd2, w, y, M, cN, cK);
+      hipMemcpy(h0.data(), y, h0.size() * 2, hipMemcpyDeviceToHost);
+      hipLaunchKernelGGL((skinny::skinny_gemm_coal_kernel<4, 2, 2, 0>),
+                         dim3(cN / 32), dim3(256), 0, 0, xd2, w, y, M, cN, cK);
+      hipMemcpy(h1.data(), y, h1.size() * 2, hipMemcpyDeviceToHost);
+      printf("coalesced vs register kernel (WPB4): %s\n",
+             h0 == h1 ? "bit-identical PASS" : "DIFFERENT FAIL");
+    }
     printf("numerics LDS kc512: maxrelerr=%.4f %s\n", maxerr,
            maxerr < 0.02 ? "PASS" : "FAIL");
     hipFree(xd2);
@@ -530,16 +466,46 @@ int main(int argc, char** argv) {
     hipMemcpy(x, cx.data(), cx.size() * 2, hipMemcpyHostToDevice);
     double gb = (double)s.N * s.K * 2 / 1e9;
     printf("%s K=%6d N=%6d:", s.name, s.K, s.N);
+#define RUN1(WPB, U, NT, NTL, RR)                                           \
+  (gb / bench(skinny_gemm_kernel<WPB, U, NT, NTL>,                          \
+              (s.N + NT * 16 - 1) / (NT * 16), WPB * 64, x, w, y, M, s.N,   \
+              s.K, iters, RR) * 1e3)
 #define RUN(WPB, U, NT)                                                     \
   {                                                                         \
-    double us = bench(skinny_gemm_kernel<WPB, U, NT>,                       \
-                      (s.N + NT * 16 - 1) / (NT * 16), WPB * 64, x, w, y,   \
-                      M, s.N, s.K, iters);                                  \
-    printf("  w%du%dn%d %6.1fus %5.2fTB/s", WPB, U, NT, us, gb / us * 1e3); \
+    double hd = RUN1(WPB, U, NT, 0, 1), hn = RUN1(WPB, U, NT, 1, 1);        \
+    double cd = RUN1(WPB, U, NT, 0, R), cn = RUN1(WPB, U, NT, 1, R);        \
+    printf("\n    w%du%dn%d  hot d %5.2f nt %5.2f | cold d %5.2f nt %5.2f "  \
+           "TB/s (%6.1f us)", WPB, U, NT, hd, hn, cd, cn, gb / cn * 1e3);   \
   }
-    RUN(4, 4, 2) RUN(4, 4, 4) RUN(4, 2, 4) RUN(2, 4, 4) RUN(2, 8, 4)
+    // R copies of W: at least 1 GiB in rotation, never the same buffer twice
+    const size_t wbytes = (size_t)s.N * s.K * 2;
+    const int R = (int)std::max<size_t>(2, (((size_t)1 << 30) + wbytes - 1) / wbytes);
+    printf(" R=%d", R);
+    SKINNY_GEMM_CONFIGS(RUN)
+#undef RUN
+#undef RUN1
+    // row-coalesced loads + ds_bpermute (U2 counts 64-k double steps)
+#define RUNQ1(WPB, U2, NT, NTL, RR)                                         \
+  (gb / bench(skinny::skinny_gemm_coal_kernel<WPB, U2, NT, NTL>,            \
+              (s.N + NT * 16 - 1) / (NT * 16), WPB * 64, x, w, y, M, s.N,   \
+              s.K, iters, RR) * 1e3)
+#define RUNQ(WPB, U2, NT)                                                   \
+  {                                                                         \
+    double hd = RUNQ1(WPB, U2, NT, 0, 1), hn = RUNQ1(WPB, U2, NT, 1, 1);    \
+    double cd = RUNQ1(WPB, U2, NT, 0, R), cn = RUNQ1(WPB, U2, NT, 1, R);    \
+    printf("\n    COAL w%du%dn%d  hot d %5.2f nt %5.2f | cold d %5.2f nt "   \
+           "%5.2f TB/s (%6.1f us)", WPB, U2, NT, hd, hn, cd, cn,            \
+           gb / cd * 1e3);                                                  \
+  }
+    RUNQ(4, 2, 2) RUNQ(8, 2, 2) RUNQ(8, 1, 4) RUNQ(8, 2, 4) RUNQ(4, 2, 4)
+    RUNQ(8, 4, 2) RUNQ(2, 2, 4) RUNQ(2, 2, 8) RUNQ(4, 1, 8) RUNQ(8, 1, 2)
+    // no K split: one wave sums all of K in order (bit-identical to the
+    // library's gate/up kernel)
+    RUNQ(1, 4, 2) RUNQ(1, 2, 4) RUNQ(1, 4, 4) RUNQ(1, 8, 2) RUNQ(1, 2, 2)
+    RUNQ(1, 1, 8) RUNQ(1, 2, 8)
+#undef RUNQ
+#undef RUNQ1
     printf("\n        ");
-    RUN(1, 8, 4) RUN(1, 4, 8) RUN(2, 4, 8) RUN(4, 8, 2) RUN(2, 2, 8)
     #define RUNC(U, NT)                                                         \
   {                                                                         \
     double us = bench(stream_ceiling_kernel<U, NT>,                         \

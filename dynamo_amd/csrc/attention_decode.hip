@@ -8,6 +8,10 @@
 
 using namespace decode_attn;
 
+// DYNAMO_DECODE_NT default, decided by the in-situ phase-1 trace row:
+// nt K/V loads measured 105 -> 123 us per layer (profiles/README.md)
+static constexpr bool kDecodeNtDefault = false;
+
 int64_t paged_decode_num_chunks(int64_t max_ctx) {
   const int chunk = decode_chunk_tokens((int)max_ctx);
   return std::max<int64_t>(1, (max_ctx + chunk - 1) / chunk);
@@ -23,7 +27,8 @@ void paged_attention_decode(torch::Tensor out, torch::Tensor q,
                             torch::Tensor partial, torch::Tensor ml,
                             double scale, int64_t chunk_tokens,
                             bool v_transposed,
-                            c10::optional<torch::Tensor> chunk_cnt) {
+                            c10::optional<torch::Tensor> chunk_cnt,
+                            int64_t nt_policy) {
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16);
   TORCH_CHECK(page_table.dtype() == torch::kInt32 && ctx_lens.dtype() == torch::kInt32);
   const bool fp8 = kcache.dtype() == torch::kFloat8_e4m3fn;
@@ -89,8 +94,20 @@ void paged_attention_decode(torch::Tensor out, torch::Tensor q,
       const char* e = getenv("DYNAMO_VT3_VARIANT");
       return e ? atoi(e) : 0;
     }();
-    if (fp8)
+    // non-temporal K/V loads for the production VT4 variants (bf16, fp8):
+    // DYNAMO_DECODE_NT, overridable per call (nt_policy 0/1) so a test can
+    // compare both variants in one process. Outputs are bit-identical.
+    static const bool nt_env = [] {
+      const char* e = getenv("DYNAMO_DECODE_NT");
+      return e == nullptr ? kDecodeNtDefault : e[0] != '0';
+    }();
+    const bool use_nt = nt_policy < 0 ? nt_env : nt_policy != 0;
+    if (fp8 && use_nt)
+      launch_vt(&paged_decode_mfma_swapped<1, 1, 0, 1, 72, 0, 4, 0, 1, 1>);
+    else if (fp8)
       launch_vt(&paged_decode_mfma_swapped<1, 1, 0, 1, 72, 0, 4>);
+    else if (vt3v == 0 && use_nt)
+      launch_vt(&paged_decode_mfma_swapped<1, 1, 0, 0, 72, 0, 4, 0, 1, 1>);
     else if (vt3v == 1)
       launch_vt(&paged_decode_mfma_swapped<1, 1, 0, 0, 72, 0, 3, 0, 2>);
     else if (vt3v == 2)

@@ -627,8 +627,13 @@ inline int mfma_lds_bytes(int G, int hd) {
 // MINW: minimum waves/SIMD the register allocator must honor (the VT2
 // double-buffer costs 285 VGPR+AGPR = 1 wave/SIMD; forcing 2 trades
 // registers for occupancy - decide by measurement, watch ScratchSize)
+// NTKV: every K and V load (ld8) uses the non-temporal cache policy
+// (global_load ... nt). K/V bytes are read once per step by one wave, so
+// they need not displace Q, the page table or the partials in the caches.
+// Arithmetic and load addresses are unchanged: outputs are bit-identical.
 template <int DEFER = 1, int PRIO = 1, int KPF = 0, int FP8 = 0,
-          int VS = 80, int XK2 = 0, int VT = 0, int LG2 = 0, int MINW = 1>
+          int VS = 80, int XK2 = 0, int VT = 0, int LG2 = 0, int MINW = 1,
+          int NTKV = 0>
 __global__ __launch_bounds__(kBlock, MINW) void paged_decode_mfma_swapped(
     float* __restrict__ partial, float* __restrict__ ml,
     short* __restrict__ out, const short* __restrict__ q,
@@ -742,11 +747,19 @@ __global__ __launch_bounds__(kBlock, MINW) void paged_decode_mfma_swapped(
     if constexpr (FP8) {
       const unsigned char* b =
           reinterpret_cast<const unsigned char*>(base) + elem_off;
-      uchar8 raw = *reinterpret_cast<const uchar8*>(b);
+      uchar8 raw;
+      if constexpr (NTKV)
+        raw = __builtin_nontemporal_load(reinterpret_cast<const uchar8*>(b));
+      else
+        raw = *reinterpret_cast<const uchar8*>(b);
       bf16x8 cv = fp8x8_to_bf16x8(raw);
       return *reinterpret_cast<short8*>(&cv);
     } else {
-      return *reinterpret_cast<const short8*>(base + elem_off);
+      if constexpr (NTKV)
+        return __builtin_nontemporal_load(
+            reinterpret_cast<const short8*>(base + elem_off));
+      else
+        return *reinterpret_cast<const short8*>(base + elem_off);
     }
   };
   auto load_k = [&](int t0_, short8 (&kf)[8]) {

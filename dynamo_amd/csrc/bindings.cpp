@@ -37,7 +37,8 @@ void paged_attention_decode(torch::Tensor out, torch::Tensor q, torch::Tensor kc
                             torch::Tensor ctx_lens, torch::Tensor partial,
                             torch::Tensor ml, double scale,
                             int64_t chunk_tokens, bool v_transposed,
-                            c10::optional<torch::Tensor> chunk_cnt);
+                            c10::optional<torch::Tensor> chunk_cnt,
+                            int64_t nt_policy);
 // attention_prefill.hip
 void attention_prefill_paged(torch::Tensor out, torch::Tensor q,
                              torch::Tensor kcache, torch::Tensor vcache,
@@ -54,6 +55,10 @@ void topkp_sample(torch::Tensor out, torch::Tensor logits,
 void gumbel_sample(torch::Tensor out, torch::Tensor logits, torch::Tensor inv_temp,
                    int64_t seed, c10::optional<torch::Tensor> row_seeds,
                    bool allow_fast);
+// skinny_gemm.hip
+void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
+                 int64_t wpb, int64_t u, int64_t nt, bool nontemporal,
+                 bool coalesced);
 // moe.hip
 void moe_grouped_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                       torch::Tensor tiles);
@@ -101,7 +106,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("page_table"), py::arg("ctx_lens"), py::arg("partial"),
         py::arg("ml"), py::arg("scale"), py::arg("chunk_tokens"),
         py::arg("v_transposed") = false,
-        py::arg("chunk_cnt") = py::none());
+        py::arg("chunk_cnt") = py::none(), py::arg("nt_policy") = -1);
   m.def("attention_prefill_paged", &attention_prefill_paged,
         py::arg("out"), py::arg("q"), py::arg("kcache"), py::arg("vcache"),
         py::arg("page_table"), py::arg("tile_seq"), py::arg("tile_q0"),
@@ -115,6 +120,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topkp_sample", &topkp_sample, py::arg("out"), py::arg("logits"),
         py::arg("inv_temp"), py::arg("top_k"), py::arg("top_p"),
         py::arg("seed"), py::arg("row_seeds") = py::none());
+  // y = x @ w^T for 1 <= M <= 16 (decode); raises on anything the kernel
+  // does not handle - dispatch and fallback live in ops.linear
+  m.def("skinny_gemm", &skinny_gemm, py::arg("y"), py::arg("x"), py::arg("w"),
+        py::arg("wpb") = 4, py::arg("u") = 4, py::arg("nt") = 2,
+        py::arg("nontemporal") = false, py::arg("coalesced") = false);
   m.def("moe_grouped_gemm", &moe_grouped_gemm);
   m.def("moe_grouped_gemm_seg", &moe_grouped_gemm_seg);
   m.def("topk_gating", &topk_gating);

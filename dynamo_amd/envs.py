@@ -35,6 +35,12 @@ ENV_VARS = {
         "5=VT5 (recorded-negative V-LDS variant)",
     "DYNAMO_FUSED_MERGE":
         "1 = fused decode chunk merge (recorded-negative; threadfence cost)",
+    "DYNAMO_DECODE_NT":
+        "1 = non-temporal K/V loads in the d-major (VT4) decode attention "
+        "kernel (bit-identical outputs; recorded-negative, slower)",
+    "DYNAMO_SKINNY_GEMM":
+        "0 = every decode weight GEMM on hipBLASLt (default: the in-tree "
+        "skinny-M kernel on the shapes in ops.SKINNY_GEMM_SHAPES)",
     "DYNAMO_MOE_BMM": "0 = grouped-kernel MoE decode instead of padded bmm",
     "DYNAMO_MOE_MFMA": "0 = VALU grouped MoE GEMM",
     "DYNAMO_MOE_GRAPHS": "0 = exclude MoE layers from hipGraph capture",

@@ -50,12 +50,12 @@ class AttnMetadata:
 
 
 def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    return F.linear(x, w)
+    return ops.linear(x, w)
 
 
 def linear_lora(x: torch.Tensor, w: torch.Tensor, lora, key: str) -> torch.Tensor:
-    """F.linear plus the active LoRA low-rank delta, if any."""
-    y = F.linear(x, w)
+    """Base product plus the active LoRA low-rank delta, if any."""
+    y = ops.linear(x, w)
     if lora is not None and key in lora:
         A, B, scale = lora[key]
         y = y + F.linear(F.linear(x, A), B) * scale

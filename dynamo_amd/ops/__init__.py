@@ -41,6 +41,71 @@ def hip_available() -> bool:
 
 
 # --------------------------------------------------------------------------
+# Decode weight GEMMs: (N, K) -> (WPB, U, NT, non-temporal W loads,
+# row-coalesced kernel) of the in-tree skinny-M kernel
+# (csrc/skinny_gemm_impl.h). A shape is listed only if (a) the kernel's
+# result is bit-identical to the library's for it, so the model computes
+# what it computed before, and (b) its in-situ trace average beat
+# hipBLASLt's in both of two paired runs (profiles/README.md, "Decode weight
+# GEMMs in-tree"). Everything else stays on the library.
+SKINNY_GEMM_SHAPES: dict = {
+    # gate/up: hipBLASLt's kernel for it sums K in order in one accumulator
+    # with the same MFMA; so does WPB = 1 (0 of 917504 outputs differ)
+    (57344, 8192): (1, 2, 2, True, True),
+    # qkv (10240, 8192), o (8192, 8192), down (8192, 28672): the K-split
+    # configurations (8, 1, 4) / (8, 1, 2) / (4, 2, 2) are 1-18 % faster in
+    # situ, but the library splits K its own way there and 0.04-0.08 % of the
+    # outputs differ by a bf16 rounding flip whatever WPB is; after 40 decode
+    # steps that changes the sampled tokens. Not shipped.
+    # lm_head (128256, 8192): not shown faster in situ. Not shipped.
+}
+
+_skinny_override: "bool | None" = None
+
+
+def set_skinny_gemm(on: "bool | None") -> None:
+    """In-process override of DYNAMO_SKINNY_GEMM (None = follow the env)."""
+    global _skinny_override
+    _skinny_override = on
+
+
+def skinny_gemm_enabled() -> bool:
+    if _skinny_override is not None:
+        return _skinny_override
+    from dynamo_amd import envs
+    return envs.get("DYNAMO_SKINNY_GEMM", True, bool)
+
+
+def skinny_gemm_config(x: torch.Tensor, w: torch.Tensor):
+    """The shape's SKINNY_GEMM_SHAPES entry if x @ w^T runs on the skinny-M
+    kernel, else None."""
+    if not (x.is_cuda and x.dim() == 2 and w.dim() == 2
+            and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
+        return None
+    M, K = x.shape
+    N = w.shape[0]
+    cfg = SKINNY_GEMM_SHAPES.get((N, K))
+    if cfg is None or not 1 <= M <= 16 or w.shape[1] != K:
+        return None
+    kstep = cfg[0] * cfg[1] * (64 if len(cfg) > 4 and cfg[4] else 32)
+    if N % 16 or K < 2048 or K % kstep:
+        return None
+    if not (x.is_contiguous() and w.is_contiguous()):
+        return None
+    return cfg if skinny_gemm_enabled() else None
+
+
+def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """x @ w^T. Decode-regime calls (M <= 16) on a shipped (N, K) take the
+    in-tree weight-streaming kernel; every other call is F.linear."""
+    cfg = skinny_gemm_config(x, w)
+    if cfg is None:
+        return torch.nn.functional.linear(x, w)
+    y = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
+    hip().skinny_gemm(y, x, w, *cfg)
+    return y
+
+
 def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float,
             allow_fast: bool = True) -> torch.Tensor:
     if x.is_cuda:
@@ -144,7 +209,9 @@ class DecodeScratch:
 
 def paged_attention_decode(q, kcache, vcache, page_table, ctx_lens, scale,
                            scratch: "DecodeScratch | None" = None, out=None,
-                           v_transposed=False):
+                           v_transposed=False, nt_policy: int = -1):
+    """nt_policy: K/V load cache policy of the d-major (VT4) kernel:
+    -1 = DYNAMO_DECODE_NT, 0 = default policy, 1 = non-temporal."""
     if q.is_cuda:
         if out is None:
             out = torch.empty_like(q)
@@ -153,7 +220,7 @@ def paged_attention_decode(q, kcache, vcache, page_table, ctx_lens, scale,
         hip().paged_attention_decode(out, q, kcache, vcache, page_table,
                                      ctx_lens, partial, ml, scale,
                                      scratch.chunk_tokens, v_transposed,
-                                     scratch.chunk_cnt)
+                                     scratch.chunk_cnt, nt_policy)
         return out
     r = torch_ref.paged_attention_decode(q, kcache, vcache, page_table,
                                          ctx_lens, scale,

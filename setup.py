@@ -25,6 +25,7 @@ hip_sources = [
         "cache.hip",
         "attention_decode.hip",
         "attention_prefill.hip",
+        "skinny_gemm.hip",
         "sampling.hip",
         "moe.hip",
         "ipc.hip",
