@@ -186,13 +186,14 @@ def bench_gemm(M=16, K=8192, N=8192):
           f"{gb/t:7.2f} GB/s")
 
 
-def bench_skinny_gemm(M=16):
+def bench_skinny_gemm(M=16, sweep=False):
     """Decode weight GEMMs at the flagship shapes, cache-cold: launch i reads
     copy i % R of W, R * bytes(W) >= 1 GiB (the step never re-reads a matrix
     before 137 GB of other weights have passed). hipBLASLt under the
     project's TunableOp table vs the in-tree kernel at the shape's shipped
     configuration (row-coalesced WPB8/U1/NT2 where the shape is not shipped),
-    with non-temporal and with default-policy W loads."""
+    with non-temporal and with default-policy W loads; then the W8A16 kernel
+    on e4m3 copies of the same matrices (`sweep`: at every configuration)."""
     from dynamo_amd.utils import enable_tunableop
     enable_tunableop(tuning=False)
     x_by_k = {}
@@ -218,18 +219,53 @@ def bench_skinny_gemm(M=16):
             ops.hip().skinny_gemm(y, x, ws[i[0] % R], *cfg[:3], nontemporal,
                                   cfg[4])
 
-        ts = {"lib": [], "nt": [], "dflt": []}
+        # the in-tree bf16 kernel stops at M = 16
+        ts = {"lib": [], "nt": [], "dflt": []} if M <= 16 else {"lib": []}
         for _ in range(3):
             ts["lib"].append(timeit(lib, iters=24))
-            ts["nt"].append(timeit(ours, iters=24))
-            ts["dflt"].append(timeit(lambda: ours(False), iters=24))
+            if M <= 16:
+                ts["nt"].append(timeit(ours, iters=24))
+                ts["dflt"].append(timeit(lambda: ours(False), iters=24))
         gb = wbytes / 1e9
         row = " | ".join(f"{k} {min(v)*1e6:7.1f} us {gb/min(v)/1e3:5.2f} TB/s"
                          for k, v in ts.items())
         shipped = "shipped" if (N, K) in ops.SKINNY_GEMM_SHAPES else "library"
         print(f"gemm cold {name:8s}[{M}x{K}x{N}] R={R} w{cfg[0]}u{cfg[1]}"
               f"n{cfg[2]} ({shipped}): {row}")
+        t_bf16 = min(ts["lib"] if shipped == "library" or M > 16
+                     else ts["nt"])
+        _bench_fp8_gemm(name, x, ws, y, t_bf16, sweep)
         del ws
+
+
+def _bench_fp8_gemm(name, x, ws, y, t_bf16, sweep):
+    """The W8A16 kernel on the same shape, cache-cold the same way (R8
+    copies of the e4m3 matrix, R8 * bytes >= 1 GiB); bytes/s are of W.
+    `t_bf16` is the time of the current bf16 dispatch for the shape. With
+    `sweep`, every launchable configuration instead of the dispatch's."""
+    M, K = x.shape
+    N = ws[0].shape[0]
+    wbytes = N * K
+    R8 = max(2, -(-(1 << 30) // wbytes))
+    qs, scale = [], None
+    for r in range(R8):
+        q, scale = ops.quantize_fp8_rowwise(ws[r % len(ws)])
+        qs.append(q)
+    i = [0]
+    cfgs = (ops.FP8_GEMM_CONFIGS if sweep
+            else (ops.fp8_gemm_config(M, N, K),))
+    for cfg in cfgs:
+        if K % (cfg[0] * 128 * cfg[1]):
+            continue
+
+        def fp8():
+            i[0] += 1
+            ops.hip().fp8_skinny_gemm(y, x, qs[i[0] % R8], scale, *cfg)
+
+        t = min(timeit(fp8, iters=24) for _ in range(3))
+        print(f"gemm cold {name:8s}[{M}x{K}x{N}] R={R8} fp8 w{cfg[0]}u{cfg[1]}"
+              f"n{cfg[2]}: {t*1e6:7.1f} us {wbytes/1e9/t/1e3:5.2f} TB/s "
+              f"({t_bf16/t:4.2f}x the bf16 dispatch)")
 
 
 if __name__ == "__main__":
@@ -268,3 +304,9 @@ if __name__ == "__main__":
         bench_gemm()
         bench_gemm(M=8192)
         bench_skinny_gemm()
+        bench_skinny_gemm(M=64)
+    if w == "fp8sweep":
+        # every launchable W8A16 configuration per shape: picks
+        # ops.FP8_GEMM_SHAPES
+        bench_skinny_gemm(sweep=True)
+        bench_skinny_gemm(M=64, sweep=True)

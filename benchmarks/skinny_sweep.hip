@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "skinny_gemm_impl.h"
+#include "fp8_gemm_impl.h"
 
 using skinny::skinny_gemm_kernel;  // the register-streaming kernel
 
@@ -360,6 +361,32 @@ static double bench(void (*kern)(const short*, const short*, short*, int, int,
   return ms * 1e3 / iters;  // us
 }
 
+// the W8A16 kernel's signature: e4m3 W plus one fp32 scale per row
+static double bench8(void (*kern)(const short*, const unsigned char*,
+                                  const float*, short*, int, int, int),
+                     int grid, int block, const short* x,
+                     const unsigned char* w, const float* scale, short* y,
+                     int M, int N, int K, int iters, int R = 1) {
+  const size_t stride = (size_t)N * K;
+  for (int i = 0; i < 5; i++)
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, 0, x,
+                       w + (i % R) * stride, scale, y, M, N, K);
+  hipEvent_t a, b;
+  hipEventCreate(&a);
+  hipEventCreate(&b);
+  hipEventRecord(a);
+  for (int i = 0; i < iters; i++)
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, 0, x,
+                       w + ((i + 5) % R) * stride, scale, y, M, N, K);
+  hipEventRecord(b);
+  hipEventSynchronize(b);
+  float ms;
+  hipEventElapsedTime(&ms, a, b);
+  hipEventDestroy(a);
+  hipEventDestroy(b);
+  return ms * 1e3 / iters;  // us
+}
+
 static short f2b(float f) {
   unsigned u;
   __builtin_memcpy(&u, &f, 4);
@@ -375,14 +402,15 @@ static float b2f(short s) {
 struct Shape { const char* name; int K, N; };
 
 int main(int argc, char** argv) {
-  const int M = argc > 1 ? atoi(argv[1]) : 16;
+  // the bf16 kernels use the first 16 rows; the FP8 rows run M up to 64
+  const int M = std::min(argc > 1 ? atoi(argv[1]) : 16, 64);
   Shape shapes[] = {
       {"qkv   ", 8192, 10240},  {"o     ", 8192, 8192},
       {"gateup", 8192, 57344},  {"down  ", 28672, 8192},
       {"lmhead", 8192, 128256},
   };
   const int maxK = 28672, maxN = 128256;
-  std::vector<short> hx(16 * maxK), hw((size_t)1 << 25);
+  std::vector<short> hx(64 * maxK), hw((size_t)1 << 25);
   srand(7);
   for (auto& v : hx) v = f2b((rand() % 2000 - 1000) / 1000.f);
   for (auto& v : hw) v = f2b((rand() % 2000 - 1000) / 1000.f);
@@ -399,7 +427,13 @@ int main(int argc, char** argv) {
     hipMemcpy(w + off, hw.data(), n * 2, hipMemcpyHostToDevice);
   }
   hipMemcpy(x, hx.data(), hx.size() * 2, hipMemcpyHostToDevice);
-  hipMalloc(&y, (size_t)16 * maxN * 2);
+  hipMalloc(&y, (size_t)64 * maxN * 2);
+  float* wscale;
+  {
+    std::vector<float> hs(maxN, 1.f / 448);
+    hipMalloc(&wscale, hs.size() * 4);
+    hipMemcpy(wscale, hs.data(), hs.size() * 4, hipMemcpyHostToDevice);
+  }
 
   // numerics check on a small shape
   {
@@ -505,6 +539,32 @@ int main(int argc, char** argv) {
     RUNQ(1, 1, 8) RUNQ(1, 2, 8)
 #undef RUNQ
 #undef RUNQ1
+    // W8A16 (fp8_gemm_impl.h): the same pool read as e4m3 bytes, nt W loads,
+    // cold over R8 copies (R8 * bytes >= 1 GiB); TB/s are of the e4m3 W.
+    // Timing only: arbitrary bytes include the NaN codes.
+    {
+      const size_t w8bytes = (size_t)s.N * s.K;
+      const int R8 = (int)std::max<size_t>(
+          2, (((size_t)1 << 30) + w8bytes - 1) / w8bytes);
+      const double gb8 = (double)w8bytes / 1e9;
+      printf("\n    FP8 R=%d", R8);
+#define RUNF1(WPB, U, NT, MT, RR)                                           \
+  (gb8 / bench8(fp8gemm::fp8_skinny_gemm_kernel<WPB, U, NT, MT, 1>,         \
+                (s.N + NT * 16 - 1) / (NT * 16), WPB * 64, x,               \
+                (const unsigned char*)w, wscale, y, M, s.N, s.K, iters, RR) \
+   * 1e3)
+#define RUNF(WPB, U, NT)                                                    \
+  if (s.K % (WPB * 128 * U) == 0) {                                         \
+    double h = M <= 16 ? RUNF1(WPB, U, NT, 1, 1) : RUNF1(WPB, U, NT, 4, 1); \
+    double c = M <= 16 ? RUNF1(WPB, U, NT, 1, R8)                           \
+                       : RUNF1(WPB, U, NT, 4, R8);                          \
+    printf("\n    FP8 w%du%dn%d  hot %5.2f | cold %5.2f TB/s (%6.1f us)",    \
+           WPB, U, NT, h, c, gb8 / c * 1e3);                                \
+  }
+      FP8_GEMM_CONFIGS(RUNF)
+#undef RUNF
+#undef RUNF1
+    }
     printf("\n        ");
     #define RUNC(U, NT)                                                         \
   {                                                                         \

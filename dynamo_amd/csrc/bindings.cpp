@@ -59,6 +59,11 @@ void gumbel_sample(torch::Tensor out, torch::Tensor logits, torch::Tensor inv_te
 void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                  int64_t wpb, int64_t u, int64_t nt, bool nontemporal,
                  bool coalesced);
+// fp8_gemm.hip
+void fp8_skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor wq,
+                     torch::Tensor scale, int64_t wpb, int64_t u, int64_t nt,
+                     bool nontemporal);
+void fp8_dequant(torch::Tensor out, torch::Tensor wq, torch::Tensor scale);
 // moe.hip
 void moe_grouped_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                       torch::Tensor tiles);
@@ -125,6 +130,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm", &skinny_gemm, py::arg("y"), py::arg("x"), py::arg("w"),
         py::arg("wpb") = 4, py::arg("u") = 4, py::arg("nt") = 2,
         py::arg("nontemporal") = false, py::arg("coalesced") = false);
+  // W8A16: y = (x @ bf16(wq)^T) * scale for 1 <= M <= 64, e4m3 weights with
+  // one fp32 scale per row; raises on anything the kernel does not handle -
+  // dispatch lives in ops.linear
+  m.def("fp8_skinny_gemm", &fp8_skinny_gemm, py::arg("y"), py::arg("x"),
+        py::arg("wq"), py::arg("scale"), py::arg("wpb") = 1, py::arg("u") = 1,
+        py::arg("nt") = 2, py::arg("nontemporal") = true);
+  m.def("fp8_dequant", &fp8_dequant, py::arg("out"), py::arg("wq"),
+        py::arg("scale"));
   m.def("moe_grouped_gemm", &moe_grouped_gemm);
   m.def("moe_grouped_gemm_seg", &moe_grouped_gemm_seg);
   m.def("topk_gating", &topk_gating);

@@ -139,6 +139,12 @@ class EngineConfig:
     # requires GQA group in 2/4/8/16 and head_dim 128 - reference parity
     # with its engines' --kv-cache-dtype fp8)
     kv_cache_dtype: str = "auto"
+    # Storage of the dense projection weights (qkv, o, gate/up, down):
+    # "bf16" keeps the compute dtype, unquantised; "fp8" stores OCP e4m3
+    # with one fp32 scale per output row (W8A16: half the weight bytes per
+    # decode step, and the freed HBM goes to the KV pool); "auto" follows
+    # DYNAMO_WEIGHT_DTYPE, whose default is bf16. llama/qwen2 only.
+    weight_dtype: str = "auto"          # auto | bf16 | fp8
     # waiting-queue admission policy (reference parity: kv-router
     # scheduling/policy.rs SchedulingPolicy FCFS/LCFS/WSPT):
     #   fcfs = arrival order; lcfs = newest first; wspt = shortest
@@ -178,6 +184,21 @@ class EngineConfig:
              if m.num_kv_heads and m.num_q_heads % m.num_kv_heads == 0 else 0)
         return (self.device.startswith("cuda") and m.head_dim == 128
                 and self.page_size % 32 == 0 and 2 <= g <= 16)
+
+    @property
+    def resolved_weight_dtype(self) -> str:
+        """"bf16" or "fp8": an explicit weight_dtype wins, "auto" follows
+        DYNAMO_WEIGHT_DTYPE (default bf16)."""
+        v = self.weight_dtype
+        if v == "auto":
+            from dynamo_amd import envs
+            v = envs.get("DYNAMO_WEIGHT_DTYPE", "bf16") or "bf16"
+            if v == "auto":
+                v = "bf16"
+        if v not in ("bf16", "fp8"):
+            raise ValueError(
+                f"weight_dtype must be auto, bf16 or fp8, got {v!r}")
+        return v
 
     @property
     def kv_torch_dtype(self):

@@ -27,6 +27,17 @@ class ModelRunner:
         self.dtype = cfg.torch_dtype
         self.tp = tp or TPContext(cfg.tp_size, cfg.tp_rank)
         m = cfg.model
+        self.weight_dtype = cfg.resolved_weight_dtype
+        if self.weight_dtype == "fp8":
+            if m.arch in ("opt", "mixtral"):
+                raise ValueError(
+                    f"fp8 weights are not supported for arch {m.arch!r}: "
+                    "only the llama/qwen2 dense projections have a W8A16 "
+                    "path (MoE experts and OPT layers use other kernels)")
+            if weight_pool is not None:
+                raise ValueError(
+                    "fp8 weights cannot be combined with a GMS weight pool: "
+                    "the pool shares unquantised tensors between workers")
         from dynamo_amd.models.registry import build_model
         if weight_pool is not None:
             from dynamo_amd.gms import weight_allocator
@@ -41,6 +52,10 @@ class ModelRunner:
             import logging
             logging.getLogger("dynamo_amd.engine").info(
                 "loaded %d checkpoint tensors from %s", n, m.weights_path)
+        if self.weight_dtype == "fp8":
+            # after the weights are final, before the KV pool is sized: the
+            # pool is sized from free memory and sees what quantising freed
+            ops.quantize_model_fp8(self.model)
         self.hkv_local = max(1, m.num_kv_heads // self.tp.size)
         self.hq_local = m.num_q_heads // self.tp.size
 

@@ -41,6 +41,10 @@ ENV_VARS = {
     "DYNAMO_SKINNY_GEMM":
         "0 = every decode weight GEMM on hipBLASLt (default: the in-tree "
         "skinny-M kernel on the shapes in ops.SKINNY_GEMM_SHAPES)",
+    "DYNAMO_WEIGHT_DTYPE":
+        "what EngineConfig.weight_dtype=\"auto\" resolves to: bf16 (default; "
+        "the compute dtype, unquantised) | fp8 (e4m3 projection weights, "
+        "W8A16)",
     "DYNAMO_MOE_BMM": "0 = grouped-kernel MoE decode instead of padded bmm",
     "DYNAMO_MOE_MFMA": "0 = VALU grouped MoE GEMM",
     "DYNAMO_MOE_GRAPHS": "0 = exclude MoE layers from hipGraph capture",

@@ -8,7 +8,9 @@ from __future__ import annotations
 
 import torch
 
-from . import torch_ref
+from . import fp8_weights, torch_ref
+from .fp8_weights import (Fp8Weight, quantize_fp8_rowwise,  # re-export
+                          quantize_model_fp8)
 from .torch_ref import make_cos_sin_cache  # re-export
 
 _hip_mod = None
@@ -95,9 +97,82 @@ def skinny_gemm_config(x: torch.Tensor, w: torch.Tensor):
     return cfg if skinny_gemm_enabled() else None
 
 
-def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+# --------------------------------------------------------------------------
+# FP8 (e4m3) weights, W8A16 (ops/fp8_weights.py, csrc/fp8_gemm_impl.h).
+# (WPB, U, NT) points of fp8_skinny_gemm the binding can launch; it needs
+# K % (WPB * 128 * U) == 0. Non-temporal W loads throughout.
+FP8_GEMM_CONFIGS: tuple = (
+    (1, 1, 1), (1, 1, 2), (1, 2, 2), (2, 1, 4), (2, 2, 2),
+    (4, 1, 2), (4, 2, 2), (4, 1, 4), (8, 1, 2), (8, 2, 2),
+)
+# The default configuration: accepts every K % 128 == 0. A shape outside the
+# table takes FP8_GEMM_SPLIT_K instead when K allows (its 4-wave K split was
+# 1.4-1.7x the bf16 dispatch on all four 70B layer shapes at M = 16, where
+# the default ranges from 0.5x to 1.6x), else the default.
+FP8_GEMM_DEFAULT: tuple = (1, 1, 2)
+FP8_GEMM_SPLIT_K: tuple = (4, 1, 2)
+# (N, K) -> ((WPB, U, NT) for M <= 16, (WPB, U, NT) for 16 < M <= 64) for the
+# llama-3-70b layer shapes: the cold-sweep winners at M = 16 and M = 64
+# (kernel_bench.py --which fp8sweep; profiles/README.md, "FP8 weights")
+FP8_GEMM_SHAPES: dict = {
+    (10240, 8192): ((4, 1, 2), (4, 1, 4)),    # qkv
+    (8192, 8192): ((8, 1, 2), (4, 1, 2)),     # o
+    (57344, 8192): ((4, 1, 4), (2, 1, 4)),    # gate/up
+    (8192, 28672): ((4, 2, 2), (4, 1, 2)),    # down
+}
+FP8_GEMM_MAX_M = 64
+
+
+def fp8_gemm_config(M: int, N: int, K: int):
+    """The (WPB, U, NT) fp8_skinny_gemm runs an [M, K] x [N, K]^T call at, or
+    None if the kernel does not take the shape."""
+    if not (1 <= M <= FP8_GEMM_MAX_M and K >= 128 and K % 128 == 0
+            and N >= 16 and N % 16 == 0):
+        return None
+    entry = FP8_GEMM_SHAPES.get((N, K))
+    cfg = entry[0 if M <= 16 else 1] if entry else FP8_GEMM_SPLIT_K
+    if K % (cfg[0] * 128 * cfg[1]):
+        cfg = FP8_GEMM_DEFAULT
+    return cfg
+
+
+def fp8_linear_path(x: torch.Tensor, w: Fp8Weight):
+    """Where linear(x, w) runs for an Fp8Weight: ("kernel", (WPB, U, NT)) for
+    the in-tree W8A16 kernel, ("dequant", None) for fp8_dequant into the
+    scratch buffer + the library GEMM, ("torch", None) for F.linear(x, W_eff)
+    with W_eff formed by torch (CPU, or a GPU call fp8_dequant cannot
+    serve)."""
+    N, K = w.shape
+    if not x.is_cuda:
+        return "torch", None
+    if x.dtype != torch.bfloat16 or K % 16 or x.shape[-1] != K:
+        return "torch", None
+    if x.dim() == 2 and x.is_contiguous() and x.data_ptr() % 16 == 0:
+        cfg = fp8_gemm_config(x.shape[0], N, K)
+        if cfg is not None:
+            return "kernel", cfg
+    return "dequant", None
+
+
+def _linear_fp8(x: torch.Tensor, w: Fp8Weight) -> torch.Tensor:
+    path, cfg = fp8_linear_path(x, w)
+    if path == "kernel":
+        y = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
+        hip().fp8_skinny_gemm(y, x, w.q, w.scale, *cfg, True)
+        return y
+    if path == "dequant":
+        w_eff = fp8_weights.scratch_view(w)
+        hip().fp8_dequant(w_eff, w.q, w.scale)
+        return torch.nn.functional.linear(x, w_eff)
+    return torch.nn.functional.linear(x, w.effective(x.dtype))
+
+
+def linear(x: torch.Tensor, w) -> torch.Tensor:
     """x @ w^T. Decode-regime calls (M <= 16) on a shipped (N, K) take the
-    in-tree weight-streaming kernel; every other call is F.linear."""
+    in-tree weight-streaming kernel; every other call is F.linear. An
+    Fp8Weight goes through fp8_linear_path."""
+    if isinstance(w, Fp8Weight):
+        return _linear_fp8(x, w)
     cfg = skinny_gemm_config(x, w)
     if cfg is None:
         return torch.nn.functional.linear(x, w)
