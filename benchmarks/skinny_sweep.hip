@@ -21,10 +21,11 @@
 //   N-tiles and a K/WPB slice; the WPB waves of a block LDS-reduce their
 //   fp32 accumulators and wave 0 writes bf16.
 //
-// "COAL" rows are skinny_gemm_coal_kernel, the row-coalesced variant that
+// "COAL" rows are the kernel's Bf16Coal format, the row-coalesced one that
 // production runs (8 rows x 128 B per load + ds_bpermute; its U counts 64-k
-// double steps). The LDS-staged, persistent and ceiling kernels below are the
-// round-2 experiments, same-buffer only.
+// steps), "FP8" rows its Fp8Coal format (W8A16, U counts 128-k steps). The
+// LDS-staged, persistent and ceiling kernels below are the round-2
+// experiments, same-buffer only.
 //
 // Each (WPB, U, NT) point runs with default-policy W loads ("d") and with
 // non-temporal ones ("nt"); x is always on the default policy.
@@ -39,9 +40,11 @@
 #include <vector>
 
 #include "skinny_gemm_impl.h"
-#include "fp8_gemm_impl.h"
 
-using skinny::skinny_gemm_kernel;  // the register-streaming kernel
+using skinny::skinny_gemm_kernel;
+using skinny::Bf16Plain;  // the register-streaming format
+using skinny::Bf16Coal;
+using skinny::Fp8Coal;
 
 // LDS-staged skinny GEMM: one 16-col n-tile per block, 4 waves. W tiles
 // (16 rows x KC cols) are staged cooperatively with fully-linear 1KB
@@ -336,48 +339,21 @@ __global__ __launch_bounds__(256) void stream_ceiling_kernel(
 }
 
 // ---------------------------------------------------------------------------
-static double bench(void (*kern)(const short*, const short*, short*, int, int,
-                                 int),
-                    int grid, int block, const short* x, const short* w,
-                    short* y, int M, int N, int K, int iters, int R = 1) {
-  // launch i reads W copy i % R (copies are N*K elements apart)
-  const size_t stride = (size_t)N * K;
+// Times kern(x, W copy, rest...): launch i reads W copy i % R, the copies
+// being `stride` elements apart.
+template <class Kern, class W, class... Rest>
+static double bench(Kern kern, int grid, int block, int iters, int R,
+                    size_t stride, const short* x, const W* w, Rest... rest) {
   for (int i = 0; i < 5; i++)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, 0, x,
-                       w + (i % R) * stride, y, M, N, K);
+                       w + (i % R) * stride, rest...);
   hipEvent_t a, b;
   hipEventCreate(&a);
   hipEventCreate(&b);
   hipEventRecord(a);
   for (int i = 0; i < iters; i++)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, 0, x,
-                       w + ((i + 5) % R) * stride, y, M, N, K);
-  hipEventRecord(b);
-  hipEventSynchronize(b);
-  float ms;
-  hipEventElapsedTime(&ms, a, b);
-  hipEventDestroy(a);
-  hipEventDestroy(b);
-  return ms * 1e3 / iters;  // us
-}
-
-// the W8A16 kernel's signature: e4m3 W plus one fp32 scale per row
-static double bench8(void (*kern)(const short*, const unsigned char*,
-                                  const float*, short*, int, int, int),
-                     int grid, int block, const short* x,
-                     const unsigned char* w, const float* scale, short* y,
-                     int M, int N, int K, int iters, int R = 1) {
-  const size_t stride = (size_t)N * K;
-  for (int i = 0; i < 5; i++)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, 0, x,
-                       w + (i % R) * stride, scale, y, M, N, K);
-  hipEvent_t a, b;
-  hipEventCreate(&a);
-  hipEventCreate(&b);
-  hipEventRecord(a);
-  for (int i = 0; i < iters; i++)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, 0, x,
-                       w + ((i + 5) % R) * stride, scale, y, M, N, K);
+                       w + ((i + 5) % R) * stride, rest...);
   hipEventRecord(b);
   hipEventSynchronize(b);
   float ms;
@@ -445,8 +421,10 @@ int main(int argc, char** argv) {
     short* xd2;
     hipMalloc(&xd2, cx.size() * 2);
     hipMemcpy(xd2, cx.data(), cx.size() * 2, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL((skinny_gemm_kernel<4, 4, 2, 1>), dim3(cN / 32),
-                       dim3(256), 0, 0, xd2, w, y, M, cN, cK);
+    const float* noscale = nullptr;
+    hipLaunchKernelGGL((skinny_gemm_kernel<Bf16Plain, 4, 4, 2, 1, 1>),
+                       dim3(cN / 32), dim3(256), 0, 0, xd2, w, noscale, y, M,
+                       cN, cK);
     hipMemcpy(hy.data(), y, hy.size() * 2, hipMemcpyDeviceToHost);
     double maxerr = 0;
     for (int m = 0; m < M; m++)
@@ -474,14 +452,16 @@ int main(int argc, char** argv) {
         maxerr = std::max(maxerr, err);
       }
     {
-      // the row-coalesced variant must reproduce skinny_gemm_kernel bit for
-      // bit at equal WPB
+      // the row-coalesced format must reproduce the register-streaming one
+      // bit for bit at equal WPB
       std::vector<short> h0(M * cN), h1(M * cN);
-      hipLaunchKernelGGL((skinny_gemm_kernel<4, 4, 2, 0>), dim3(cN / 32),
-                         dim3(256), 0, 0, xd2, w, y, M, cN, cK);
+      hipLaunchKernelGGL((skinny_gemm_kernel<Bf16Plain, 4, 4, 2, 1, 0>),
+                         dim3(cN / 32), dim3(256), 0, 0, xd2, w, noscale, y,
+                         M, cN, cK);
       hipMemcpy(h0.data(), y, h0.size() * 2, hipMemcpyDeviceToHost);
-      hipLaunchKernelGGL((skinny::skinny_gemm_coal_kernel<4, 2, 2, 0>),
-                         dim3(cN / 32), dim3(256), 0, 0, xd2, w, y, M, cN, cK);
+      hipLaunchKernelGGL((skinny_gemm_kernel<Bf16Coal, 4, 2, 2, 1, 0>),
+                         dim3(cN / 32), dim3(256), 0, 0, xd2, w, noscale, y,
+                         M, cN, cK);
       hipMemcpy(h1.data(), y, h1.size() * 2, hipMemcpyDeviceToHost);
       printf("coalesced vs register kernel (WPB4): %s\n",
              h0 == h1 ? "bit-identical PASS" : "DIFFERENT FAIL");
@@ -500,10 +480,14 @@ int main(int argc, char** argv) {
     hipMemcpy(x, cx.data(), cx.size() * 2, hipMemcpyHostToDevice);
     double gb = (double)s.N * s.K * 2 / 1e9;
     printf("%s K=%6d N=%6d:", s.name, s.K, s.N);
+    // rate of format F over RR copies of W (bytes GB each, at WP)
+#define RATE(F, WPB, U, NT, MT, NTL, GB, WP, SCALE, RR)                     \
+  (GB / bench(skinny_gemm_kernel<F, WPB, U, NT, MT, NTL>,                   \
+              (s.N + NT * 16 - 1) / (NT * 16), WPB * 64, iters, RR,         \
+              (size_t)s.N * s.K, x, WP, (const float*)SCALE, y, M, s.N,     \
+              s.K) * 1e3)
 #define RUN1(WPB, U, NT, NTL, RR)                                           \
-  (gb / bench(skinny_gemm_kernel<WPB, U, NT, NTL>,                          \
-              (s.N + NT * 16 - 1) / (NT * 16), WPB * 64, x, w, y, M, s.N,   \
-              s.K, iters, RR) * 1e3)
+  RATE(Bf16Plain, WPB, U, NT, 1, NTL, gb, w, nullptr, RR)
 #define RUN(WPB, U, NT)                                                     \
   {                                                                         \
     double hd = RUN1(WPB, U, NT, 0, 1), hn = RUN1(WPB, U, NT, 1, 1);        \
@@ -518,11 +502,9 @@ int main(int argc, char** argv) {
     SKINNY_GEMM_CONFIGS(RUN)
 #undef RUN
 #undef RUN1
-    // row-coalesced loads + ds_bpermute (U2 counts 64-k double steps)
+    // row-coalesced loads + ds_bpermute (U2 counts 64-k steps)
 #define RUNQ1(WPB, U2, NT, NTL, RR)                                         \
-  (gb / bench(skinny::skinny_gemm_coal_kernel<WPB, U2, NT, NTL>,            \
-              (s.N + NT * 16 - 1) / (NT * 16), WPB * 64, x, w, y, M, s.N,   \
-              s.K, iters, RR) * 1e3)
+  RATE(Bf16Coal, WPB, U2, NT, 1, NTL, gb, w, nullptr, RR)
 #define RUNQ(WPB, U2, NT)                                                   \
   {                                                                         \
     double hd = RUNQ1(WPB, U2, NT, 0, 1), hn = RUNQ1(WPB, U2, NT, 1, 1);    \
@@ -539,7 +521,7 @@ int main(int argc, char** argv) {
     RUNQ(1, 1, 8) RUNQ(1, 2, 8)
 #undef RUNQ
 #undef RUNQ1
-    // W8A16 (fp8_gemm_impl.h): the same pool read as e4m3 bytes, nt W loads,
+    // W8A16 (Fp8Coal): the same pool read as e4m3 bytes, nt W loads,
     // cold over R8 copies (R8 * bytes >= 1 GiB); TB/s are of the e4m3 W.
     // Timing only: arbitrary bytes include the NaN codes.
     {
@@ -549,10 +531,7 @@ int main(int argc, char** argv) {
       const double gb8 = (double)w8bytes / 1e9;
       printf("\n    FP8 R=%d", R8);
 #define RUNF1(WPB, U, NT, MT, RR)                                           \
-  (gb8 / bench8(fp8gemm::fp8_skinny_gemm_kernel<WPB, U, NT, MT, 1>,         \
-                (s.N + NT * 16 - 1) / (NT * 16), WPB * 64, x,               \
-                (const unsigned char*)w, wscale, y, M, s.N, s.K, iters, RR) \
-   * 1e3)
+  RATE(Fp8Coal, WPB, U, NT, MT, 1, gb8, (const unsigned char*)w, wscale, RR)
 #define RUNF(WPB, U, NT)                                                    \
   if (s.K % (WPB * 128 * U) == 0) {                                         \
     double h = M <= 16 ? RUNF1(WPB, U, NT, 1, 1) : RUNF1(WPB, U, NT, 4, 1); \
@@ -564,13 +543,14 @@ int main(int argc, char** argv) {
       FP8_GEMM_CONFIGS(RUNF)
 #undef RUNF
 #undef RUNF1
+#undef RATE
     }
     printf("\n        ");
     #define RUNC(U, NT)                                                         \
   {                                                                         \
     double us = bench(stream_ceiling_kernel<U, NT>,                         \
-                      (s.N + NT * 16 - 1) / (NT * 16), 256, x, w, y, M,     \
-                      s.N, s.K, iters);                                     \
+                      (s.N + NT * 16 - 1) / (NT * 16), 256, iters, 1, 0, x, \
+                      w, y, M, s.N, s.K);                                   \
     printf("  CEIL u%dn%d %6.1fus %5.2fTB/s", U, NT, us, gb / us * 1e3);    \
   }
     RUNC(4, 2) RUNC(4, 4) RUNC(8, 4)
@@ -580,8 +560,8 @@ int main(int argc, char** argv) {
   {                                                                         \
     int ng = (s.N + NT * 16 - 1) / (NT * 16);                               \
     double us = bench(skinny_gemm_ps_kernel<WPB, U, NT>,                    \
-                      std::min(GRID, ng), WPB * 64, x, w, y, M, s.N, s.K,   \
-                      iters);                                               \
+                      std::min(GRID, ng), WPB * 64, iters, 1, 0, x, w, y,   \
+                      M, s.N, s.K);                                         \
     printf("  PS w%du%dn%d g%d %6.1fus %5.2fTB/s", WPB, U, NT, GRID, us,    \
            gb / us * 1e3);                                                  \
   }
@@ -589,8 +569,8 @@ int main(int argc, char** argv) {
 #undef RUNP
 #define RUNL(KC)                                                            \
   {                                                                         \
-    double us = bench(skinny_gemm_lds_kernel<KC>, s.N / 16, 256, x, w, y,   \
-                      M, s.N, s.K, iters);                                  \
+    double us = bench(skinny_gemm_lds_kernel<KC>, s.N / 16, 256, iters, 1,  \
+                      0, x, w, y, M, s.N, s.K);                             \
     printf("  LDS kc%d %6.1fus %5.2fTB/s", KC, us, gb / us * 1e3);          \
   }
     RUNL(512) RUNL(1024) RUNL(2048)

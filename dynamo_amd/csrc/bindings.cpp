@@ -59,7 +59,8 @@ void gumbel_sample(torch::Tensor out, torch::Tensor logits, torch::Tensor inv_te
 void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                  int64_t wpb, int64_t u, int64_t nt, bool nontemporal,
                  bool coalesced);
-// fp8_gemm.hip
+std::map<std::string, std::vector<std::tuple<int, int, int>>>
+skinny_gemm_configs();
 void fp8_skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor wq,
                      torch::Tensor scale, int64_t wpb, int64_t u, int64_t nt,
                      bool nontemporal);
@@ -138,6 +139,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nt") = 2, py::arg("nontemporal") = true);
   m.def("fp8_dequant", &fp8_dequant, py::arg("out"), py::arg("wq"),
         py::arg("scale"));
+  // {"bf16_plain" | "bf16_coalesced" | "fp8": [(WPB, U, NT), ...]}: what the
+  // two GEMM bindings can launch
+  m.def("skinny_gemm_configs", &skinny_gemm_configs);
   m.def("moe_grouped_gemm", &moe_grouped_gemm);
   m.def("moe_grouped_gemm_seg", &moe_grouped_gemm_seg);
   m.def("topk_gating", &topk_gating);

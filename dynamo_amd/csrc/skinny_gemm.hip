@@ -1,70 +1,173 @@
-// Torch binding for the skinny-M decode weight GEMM (skinny_gemm_impl.h):
-// y[M,N] = x[M,K] @ W[N,K]^T, bf16, 1 <= M <= 16. `coalesced` selects the
-// row-coalesced kernel (u then counts 64-k double steps), `nontemporal` the
-// cache policy of the W loads.
-// The launcher uses the current stream and neither allocates nor
-// synchronises, so it can run inside the captured decode graph.
+// Torch bindings for the skinny-M decode weight GEMM and the fp8 weight
+// dequantisation (skinny_gemm_impl.h).
+//   skinny_gemm:     y[M,N] = x[M,K] @ w[N,K]^T, bf16, 1 <= M <= 16.
+//                    `coalesced` selects the row-coalesced format (u then
+//                    counts 64-k steps, else 32-k ones).
+//   fp8_skinny_gemm: y[M,N] = bf16((x[M,K] @ bf16(wq[N,K])^T) * scale[n]),
+//                    x/y bf16, wq float8_e4m3fn, scale fp32, 1 <= M <= 64;
+//                    u counts 128-k steps.
+//   fp8_dequant:     out[N,K] = bf16(float(wq[N,K]) * scale[n]).
+// `nontemporal` is the cache policy of the W loads. The launchers use the
+// current stream and neither allocate nor synchronise, so they can run inside
+// the captured decode graph.
 #include "skinny_gemm_impl.h"
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+namespace {
+
+struct GemmArgs {
+  const short* x;
+  const void* w;
+  const float* scale;   // null for the bf16 formats
+  short* y;
+  int M, N, K;
+  int64_t wpb, u, nt;
+  bool nontemporal;
+};
+
+// Everything both GEMM entry points require of their arguments but the W and
+// scale dtypes; max_m, min_k and k_per_step are the format's limits.
+GemmArgs check_args(const char* name, int64_t max_m, int64_t min_k,
+                    int64_t k_per_step, const torch::Tensor& y,
+                    const torch::Tensor& x, const torch::Tensor& w,
+                    const torch::Tensor* scale, int64_t wpb, int64_t u,
+                    int64_t nt, bool nontemporal) {
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && y.is_cuda() &&
+                  (!scale || scale->is_cuda()),
+              name, ": tensors must be on the GPU");
+  TORCH_CHECK(x.dtype() == torch::kBFloat16 && y.dtype() == torch::kBFloat16,
+              name, ": x and y must be bf16");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && y.dim() == 2 &&
+                  (!scale || scale->dim() == 1),
+              name, ": x [M,K], w [N,K], scale [N], y [M,N]");
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && y.is_contiguous() &&
+                  (!scale || scale->is_contiguous()),
+              name, ": tensors must be contiguous");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(w.size(1) == K && y.size(0) == M && y.size(1) == N &&
+                  (!scale || scale->size(0) == N),
+              name, ": shape mismatch");
+  TORCH_CHECK(M >= 1 && M <= max_m, name, ": needs 1 <= M <= ", max_m,
+              ", got ", M);
+  TORCH_CHECK(N >= 16 && N % 16 == 0, name, ": needs N % 16 == 0, got ", N);
+  TORCH_CHECK(N < (1 << 27), name, ": N too large");
+  TORCH_CHECK(wpb > 0 && u > 0 && nt > 0, name, ": bad configuration");
+  const int64_t kstep = wpb * k_per_step * u;
+  TORCH_CHECK(K >= min_k && K < (1 << 30) && K % kstep == 0, name,
+              ": needs K >= ", min_k, " and K % ", kstep, " == 0, got ", K);
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+                  (uintptr_t)w.data_ptr() % 16 == 0,
+              name, ": x and w must be 16 B aligned");
+  return {(const short*)x.data_ptr(), w.data_ptr(),
+          scale ? (const float*)scale->data_ptr() : nullptr,
+          (short*)y.data_ptr(), (int)M, (int)N, (int)K, wpb, u, nt,
+          nontemporal};
+}
+
+// Launches <F, WPB, U, NT> at ceil(M / 16) accumulator tiles, MT at the most.
+template <class F, int WPB, int U, int NT, int MT>
+void launch(const GemmArgs& a) {
+  if constexpr (MT > 1) {
+    if (a.M <= (MT - 1) * 16) return launch<F, WPB, U, NT, MT - 1>(a);
+  }
+  const int grid = (a.N + NT * 16 - 1) / (NT * 16);
+  auto stream = at::cuda::getCurrentHIPStream();
+  auto w = (const typename F::welem*)a.w;
+  if (a.nontemporal)
+    skinny::skinny_gemm_kernel<F, WPB, U, NT, MT, 1>
+        <<<grid, WPB * 64, 0, stream>>>(a.x, w, a.scale, a.y, a.M, a.N, a.K);
+  else
+    skinny::skinny_gemm_kernel<F, WPB, U, NT, MT, 0>
+        <<<grid, WPB * 64, 0, stream>>>(a.x, w, a.scale, a.y, a.M, a.N, a.K);
+}
+
+typedef std::vector<std::tuple<int, int, int>> ConfigList;
+
+// NAME(a) launches a's (wpb, u, nt) if TABLE lists it, else raises;
+// NAME_configs() is TABLE as a list.
+#define GEMM_CASE(WPB, U, NT)                                                \
+  if (a.wpb == WPB && a.u == U && a.nt == NT)                                \
+    return launch<Format, WPB, U, NT, kMaxMt>(a);
+#define GEMM_ENTRY(WPB, U, NT) {WPB, U, NT},
+#define GEMM_DISPATCH(NAME, F, MAX_MT, TABLE)                                \
+  void NAME(const char* name, const GemmArgs& a) {                           \
+    using Format = F;                                                        \
+    constexpr int kMaxMt = MAX_MT;                                           \
+    TABLE(GEMM_CASE)                                                         \
+    TORCH_CHECK(false, name, ": no kernel for (WPB, U, NT) = (", a.wpb,      \
+                ", ", a.u, ", ", a.nt, ")");                                 \
+  }                                                                          \
+  ConfigList NAME##_configs() { return {TABLE(GEMM_ENTRY)}; }
+GEMM_DISPATCH(launch_plain, skinny::Bf16Plain, 1, SKINNY_GEMM_CONFIGS)
+GEMM_DISPATCH(launch_coal, skinny::Bf16Coal, 1, SKINNY_GEMM_COAL_CONFIGS)
+GEMM_DISPATCH(launch_fp8, skinny::Fp8Coal, 4, FP8_GEMM_CONFIGS)
+#undef GEMM_DISPATCH
+#undef GEMM_ENTRY
+#undef GEMM_CASE
+
+}  // namespace
+
 void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                  int64_t wpb, int64_t u, int64_t nt, bool nontemporal,
                  bool coalesced) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda() && y.is_cuda(),
-              "skinny_gemm: tensors must be on the GPU");
-  TORCH_CHECK(x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16 &&
-                  y.dtype() == torch::kBFloat16,
-              "skinny_gemm: bf16 only");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && y.dim() == 2,
-              "skinny_gemm: x [M,K], w [N,K], y [M,N]");
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && y.is_contiguous(),
-              "skinny_gemm: x, w and y must be contiguous");
-  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(w.size(1) == K && y.size(0) == M && y.size(1) == N,
-              "skinny_gemm: shape mismatch");
-  TORCH_CHECK(M >= 1 && M <= 16, "skinny_gemm: needs 1 <= M <= 16, got ", M);
-  TORCH_CHECK(N >= 16 && N % 16 == 0, "skinny_gemm: needs N % 16 == 0, got ", N);
-  TORCH_CHECK(N < (1 << 27), "skinny_gemm: N too large");
-  TORCH_CHECK(wpb > 0 && u > 0 && nt > 0, "skinny_gemm: bad configuration");
-  const int64_t kstep = wpb * (coalesced ? 64 : 32) * u;
-  TORCH_CHECK(K >= 2048 && K < (1 << 30) && K % kstep == 0,
-              "skinny_gemm: needs K >= 2048 and K % ", kstep, " == 0, got ", K);
-  auto stream = at::cuda::getCurrentHIPStream();
-  const short* xp = (const short*)x.data_ptr();
-  const short* wp = (const short*)w.data_ptr();
-  short* yp = (short*)y.data_ptr();
-  const int grid = (int)((N + nt * 16 - 1) / (nt * 16));
+  const char* name = "skinny_gemm";
+  TORCH_CHECK(w.dtype() == torch::kBFloat16, name, ": w must be bf16");
+  const GemmArgs a = check_args(
+      name, 16, 2048,
+      coalesced ? skinny::Bf16Coal::KSTEP : skinny::Bf16Plain::KSTEP, y, x, w,
+      nullptr, wpb, u, nt, nontemporal);
+  if (coalesced) launch_coal(name, a);
+  else launch_plain(name, a);
+  HIP_CHECK_KERNEL();
+}
 
-  bool launched = false;
-#define SKINNY_CASE(WPB, U, NT)                                              \
-  if (!launched && wpb == WPB && u == U && nt == NT) {                       \
-    if (nontemporal)                                                         \
-      skinny::skinny_gemm_kernel<WPB, U, NT, 1>                              \
-          <<<grid, WPB * 64, 0, stream>>>(xp, wp, yp, (int)M, (int)N, (int)K); \
-    else                                                                     \
-      skinny::skinny_gemm_kernel<WPB, U, NT, 0>                              \
-          <<<grid, WPB * 64, 0, stream>>>(xp, wp, yp, (int)M, (int)N, (int)K); \
-    launched = true;                                                         \
-  }
-#define SKINNY_COAL_CASE(WPB, U2, NT)                                        \
-  if (!launched && wpb == WPB && u == U2 && nt == NT) {                      \
-    if (nontemporal)                                                         \
-      skinny::skinny_gemm_coal_kernel<WPB, U2, NT, 1>                        \
-          <<<grid, WPB * 64, 0, stream>>>(xp, wp, yp, (int)M, (int)N, (int)K); \
-    else                                                                     \
-      skinny::skinny_gemm_coal_kernel<WPB, U2, NT, 0>                        \
-          <<<grid, WPB * 64, 0, stream>>>(xp, wp, yp, (int)M, (int)N, (int)K); \
-    launched = true;                                                         \
-  }
-  if (coalesced) {
-    SKINNY_GEMM_COAL_CONFIGS(SKINNY_COAL_CASE)
-  } else {
-    SKINNY_GEMM_CONFIGS(SKINNY_CASE)
-  }
-#undef SKINNY_COAL_CASE
-#undef SKINNY_CASE
-  TORCH_CHECK(launched, "skinny_gemm: no kernel for (WPB, U, NT) = (", wpb,
-              ", ", u, ", ", nt, ")");
+void fp8_skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor wq,
+                     torch::Tensor scale, int64_t wpb, int64_t u, int64_t nt,
+                     bool nontemporal) {
+  const char* name = "fp8_skinny_gemm";
+  TORCH_CHECK(wq.dtype() == at::kFloat8_e4m3fn, name,
+              ": wq must be float8_e4m3fn");
+  TORCH_CHECK(scale.dtype() == torch::kFloat32, name, ": scale must be fp32");
+  launch_fp8(name, check_args(name, 64, 128, skinny::Fp8Coal::KSTEP, y, x, wq,
+                              &scale, wpb, u, nt, nontemporal));
+  HIP_CHECK_KERNEL();
+}
+
+// The (WPB, U, NT) tables of the three formats, for the Python side to check
+// its own copies against.
+std::map<std::string, ConfigList> skinny_gemm_configs() {
+  return {{"bf16_plain", launch_plain_configs()},
+          {"bf16_coalesced", launch_coal_configs()},
+          {"fp8", launch_fp8_configs()}};
+}
+
+void fp8_dequant(torch::Tensor out, torch::Tensor wq, torch::Tensor scale) {
+  TORCH_CHECK(out.is_cuda() && wq.is_cuda() && scale.is_cuda(),
+              "fp8_dequant: tensors must be on the GPU");
+  TORCH_CHECK(out.dtype() == torch::kBFloat16 &&
+                  wq.dtype() == at::kFloat8_e4m3fn &&
+                  scale.dtype() == torch::kFloat32,
+              "fp8_dequant: out bf16, wq float8_e4m3fn, scale fp32");
+  TORCH_CHECK(out.dim() == 2 && wq.dim() == 2 && scale.dim() == 1,
+              "fp8_dequant: out [N,K], wq [N,K], scale [N]");
+  TORCH_CHECK(out.is_contiguous() && wq.is_contiguous() &&
+                  scale.is_contiguous(),
+              "fp8_dequant: tensors must be contiguous");
+  const int64_t N = wq.size(0), K = wq.size(1);
+  TORCH_CHECK(out.size(0) == N && out.size(1) == K && scale.size(0) == N,
+              "fp8_dequant: shape mismatch");
+  TORCH_CHECK(N >= 1 && K >= 16 && K % 16 == 0,
+              "fp8_dequant: needs K % 16 == 0, got ", K);
+  TORCH_CHECK((uintptr_t)out.data_ptr() % 16 == 0 &&
+                  (uintptr_t)wq.data_ptr() % 16 == 0,
+              "fp8_dequant: out and wq must be 16 B aligned");
+  const int64_t threads = N * (K / 16);
+  const int64_t blocks = (threads + 255) / 256;
+  TORCH_CHECK(blocks < (1ll << 31), "fp8_dequant: matrix too large");
+  auto stream = at::cuda::getCurrentHIPStream();
+  skinny::fp8_dequant_kernel<<<(unsigned)blocks, 256, 0, stream>>>(
+      (short*)out.data_ptr(), (const unsigned char*)wq.data_ptr(),
+      (const float*)scale.data_ptr(), (long long)N, (long long)K);
   HIP_CHECK_KERNEL();
 }

@@ -89,18 +89,21 @@ def skinny_gemm_config(x: torch.Tensor, w: torch.Tensor):
     cfg = SKINNY_GEMM_SHAPES.get((N, K))
     if cfg is None or not 1 <= M <= 16 or w.shape[1] != K:
         return None
-    kstep = cfg[0] * cfg[1] * (64 if len(cfg) > 4 and cfg[4] else 32)
+    kstep = cfg[0] * cfg[1] * (64 if cfg[4] else 32)
     if N % 16 or K < 2048 or K % kstep:
         return None
-    if not (x.is_contiguous() and w.is_contiguous()):
+    if not (x.is_contiguous() and w.is_contiguous()
+            and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0):
         return None
     return cfg if skinny_gemm_enabled() else None
 
 
 # --------------------------------------------------------------------------
-# FP8 (e4m3) weights, W8A16 (ops/fp8_weights.py, csrc/fp8_gemm_impl.h).
-# (WPB, U, NT) points of fp8_skinny_gemm the binding can launch; it needs
-# K % (WPB * 128 * U) == 0. Non-temporal W loads throughout.
+# FP8 (e4m3) weights, W8A16 (ops/fp8_weights.py, the Fp8Coal format of
+# csrc/skinny_gemm_impl.h). (WPB, U, NT) points of fp8_skinny_gemm the binding
+# can launch; it needs K % (WPB * 128 * U) == 0. A copy of the header's
+# FP8_GEMM_CONFIGS that tests can read without the extension; they check it
+# against hip().skinny_gemm_configs(). Non-temporal W loads throughout.
 FP8_GEMM_CONFIGS: tuple = (
     (1, 1, 1), (1, 1, 2), (1, 2, 2), (2, 1, 4), (2, 2, 2),
     (4, 1, 2), (4, 2, 2), (4, 1, 4), (8, 1, 2), (8, 2, 2),

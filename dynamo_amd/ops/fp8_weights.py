@@ -6,10 +6,11 @@ fp32 accumulate, bf16 out). The effective weight is defined once,
 
     W_eff = (q.float() * scale[:, None]).to(compute dtype)
 
-and every path computes x @ W_eff^T: the in-tree W8A16 kernel
-(csrc/fp8_gemm_impl.h) for decode-regime calls on the GPU, fp8_dequant into a
-per-device scratch buffer followed by the library GEMM for every other GPU
-call, and F.linear(x, W_eff) on the CPU. Dispatch lives in ops.linear.
+and every path computes x @ W_eff^T: the in-tree W8A16 kernel (the Fp8Coal
+format of csrc/skinny_gemm_impl.h) for decode-regime calls on the GPU,
+fp8_dequant into a per-device scratch buffer followed by the library GEMM for
+every other GPU call, and F.linear(x, W_eff) on the CPU. Dispatch lives in
+ops.linear.
 """
 from __future__ import annotations
 

@@ -26,7 +26,6 @@ hip_sources = [
         "attention_decode.hip",
         "attention_prefill.hip",
         "skinny_gemm.hip",
-        "fp8_gemm.hip",
         "sampling.hip",
         "moe.hip",
         "ipc.hip",

@@ -1,6 +1,6 @@
 """FP8 (e4m3) weights on the GPU: the W8A16 decode GEMM and the dequantise
-kernel (csrc/fp8_gemm_impl.h), their dispatch (ops.linear with an Fp8Weight)
-and an engine built with weight_dtype="fp8".
+kernel (csrc/skinny_gemm_impl.h), their dispatch (ops.linear with an
+Fp8Weight) and an engine built with weight_dtype="fp8".
 
 Inputs are seeded: x ~ N(0, 1) in bf16, W ~ N(0, 0.02) quantised by the
 project's quantiser. The accuracy criterion has no fixed tolerance: with
@@ -84,6 +84,9 @@ def test_every_configuration(cfg, M):
 
 
 def test_default_is_launchable_and_takes_every_k():
+    launchable = ops.hip().skinny_gemm_configs()["fp8"]
+    assert len(launchable) == len(ops.FP8_GEMM_CONFIGS)
+    assert set(launchable) == set(ops.FP8_GEMM_CONFIGS)
     assert DEFAULT in ops.FP8_GEMM_CONFIGS
     assert _kstep(DEFAULT) == 128
     assert ops.FP8_GEMM_SPLIT_K in ops.FP8_GEMM_CONFIGS

@@ -116,6 +116,9 @@ def _ineligible_calls():
         "fp16": (t(16, 2048, dtype=torch.float16),
                  t(48, 2048, dtype=torch.float16, scale=0.02)),
         "non-contiguous x": (t(16, 4096)[:, :2048], t(48, 2048, scale=0.02)),
+        # contiguous, but starting 2 bytes into its buffer
+        "misaligned x": (t(16 * 2048 + 8)[1:16 * 2048 + 1].view(16, 2048),
+                         t(48, 2048, scale=0.02)),
     }
 
 
@@ -144,9 +147,11 @@ def test_dispatch_takes_kernel_when_eligible(shipped_test_shapes):
 
 
 @pytest.mark.parametrize("case", ["M=17", "K=1000", "K=1024", "N=40", "fp16",
-                                  "non-contiguous x"])
+                                  "non-contiguous x", "misaligned x"])
 def test_dispatch_ineligible_goes_to_library(shipped_test_shapes, case):
     x, w = _ineligible_calls()[case]
+    if case == "misaligned x":
+        assert x.is_contiguous() and x.data_ptr() % 16 == 2
     assert ops.skinny_gemm_config(x, w) is None
     assert torch.equal(ops.linear(x, w), F.linear(x, w))
     y = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=DEV)
@@ -185,6 +190,12 @@ def test_load_pattern_and_policy_change_no_bits():
     ref1 = _kernel(x16, w, (1, 8, 4, False, False))
     assert torch.equal(ref1, _kernel(x16, w, (1, 2, 2, True, True)))
     assert torch.equal(ref1, _kernel(x16, w, (1, 2, 4, True, True)))
+
+
+def test_shipped_configurations_are_launchable():
+    coalesced = set(ops.hip().skinny_gemm_configs()["bf16_coalesced"])
+    for cfg in SHIPPED_CFGS:
+        assert cfg[4] and cfg[:3] in coalesced
 
 
 def test_binding_rejects_unknown_configuration():
