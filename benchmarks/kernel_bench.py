@@ -186,14 +186,16 @@ def bench_gemm(M=16, K=8192, N=8192):
           f"{gb/t:7.2f} GB/s")
 
 
-def bench_skinny_gemm(M=16, sweep=False):
+def bench_skinny_gemm(M=16, sweep=False, mxfp4_sweep=False):
     """Decode weight GEMMs at the flagship shapes, cache-cold: launch i reads
     copy i % R of W, R * bytes(W) >= 1 GiB (the step never re-reads a matrix
     before 137 GB of other weights have passed). hipBLASLt under the
     project's TunableOp table vs the in-tree kernel at the shape's shipped
     configuration (row-coalesced WPB8/U1/NT2 where the shape is not shipped),
     with non-temporal and with default-policy W loads; then the W8A16 kernel
-    on e4m3 copies of the same matrices (`sweep`: at every configuration)."""
+    on e4m3 copies of the same matrices (`sweep`: at every configuration) and
+    the W4A16 kernel on MXFP4 copies (`mxfp4_sweep`: at every
+    configuration)."""
     from dynamo_amd.utils import enable_tunableop
     enable_tunableop(tuning=False)
     x_by_k = {}
@@ -235,6 +237,8 @@ def bench_skinny_gemm(M=16, sweep=False):
         t_bf16 = min(ts["lib"] if shipped == "library" or M > 16
                      else ts["nt"])
         _bench_fp8_gemm(name, x, ws, y, t_bf16, sweep)
+        if name != "lm_head":       # not quantised by weight_dtype="mxfp4"
+            _bench_mxfp4_gemm(name, x, ws, y, t_bf16, mxfp4_sweep)
         del ws
 
 
@@ -265,6 +269,38 @@ def _bench_fp8_gemm(name, x, ws, y, t_bf16, sweep):
         t = min(timeit(fp8, iters=24) for _ in range(3))
         print(f"gemm cold {name:8s}[{M}x{K}x{N}] R={R8} fp8 w{cfg[0]}u{cfg[1]}"
               f"n{cfg[2]}: {t*1e6:7.1f} us {wbytes/1e9/t/1e3:5.2f} TB/s "
+              f"({t_bf16/t:4.2f}x the bf16 dispatch)")
+
+
+def _bench_mxfp4_gemm(name, x, ws, y, t_bf16, sweep):
+    """The W4A16 kernel on the same shape, cache-cold the same way (R4
+    copies of the packed matrix and its scales, R4 * bytes >= 1 GiB);
+    bytes/s are of W, scales included. M above the kernel's limit prints
+    nothing."""
+    M, K = x.shape
+    N = ws[0].shape[0]
+    if M > ops.MXFP4_GEMM_MAX_M:
+        return
+    wbytes = N * K // 2 + N * K // 32
+    R4 = max(2, -(-(1 << 30) // wbytes))
+    first = [ops.quantize_mxfp4(w) for w in ws[:R4]]
+    qs = [first[r] if r < len(first) else
+          tuple(t.clone() for t in first[r % len(first)]) for r in range(R4)]
+    i = [0]
+    cfgs = (ops.MXFP4_GEMM_CONFIGS if sweep
+            else (ops.mxfp4_gemm_config(M, N, K),))
+    for cfg in cfgs:
+        if K % (cfg[0] * 256 * cfg[1]):
+            continue
+
+        def mxfp4():
+            i[0] += 1
+            ops.hip().mxfp4_skinny_gemm(y, x, *qs[i[0] % R4], *cfg)
+
+        t = min(timeit(mxfp4, iters=24) for _ in range(3))
+        print(f"gemm cold {name:8s}[{M}x{K}x{N}] R={R4} mxfp4 w{cfg[0]}"
+              f"u{cfg[1]}n{cfg[2]}: {t*1e6:7.1f} us "
+              f"{wbytes/1e9/t/1e3:5.2f} TB/s "
               f"({t_bf16/t:4.2f}x the bf16 dispatch)")
 
 
@@ -310,3 +346,8 @@ if __name__ == "__main__":
         # ops.FP8_GEMM_SHAPES
         bench_skinny_gemm(sweep=True)
         bench_skinny_gemm(M=64, sweep=True)
+    if w == "mxfp4sweep":
+        # every launchable W4A16 configuration per shape, next to the bf16
+        # and fp8 dispatches: picks ops.MXFP4_GEMM_SHAPES
+        bench_skinny_gemm(mxfp4_sweep=True)
+        bench_skinny_gemm(M=ops.MXFP4_GEMM_MAX_M, mxfp4_sweep=True)

@@ -23,7 +23,8 @@
 //
 // "COAL" rows are the kernel's Bf16Coal format, the row-coalesced one that
 // production runs (8 rows x 128 B per load + ds_bpermute; its U counts 64-k
-// steps), "FP8" rows its Fp8Coal format (W8A16, U counts 128-k steps). The
+// steps), "FP8" rows its Fp8Coal format (W8A16, U counts 128-k steps), "MXFP4"
+// rows its Mxfp4Coal format (W4A16, U counts 256-k steps, M <= 32). The
 // LDS-staged, persistent and ceiling kernels below are the round-2
 // experiments, same-buffer only.
 //
@@ -45,6 +46,7 @@ using skinny::skinny_gemm_kernel;
 using skinny::Bf16Plain;  // the register-streaming format
 using skinny::Bf16Coal;
 using skinny::Fp8Coal;
+using skinny::Mxfp4Coal;
 
 // LDS-staged skinny GEMM: one 16-col n-tile per block, 4 waves. W tiles
 // (16 rows x KC cols) are staged cooperatively with fully-linear 1KB
@@ -411,6 +413,10 @@ int main(int argc, char** argv) {
     hipMemcpy(wscale, hs.data(), hs.size() * 4, hipMemcpyHostToDevice);
   }
 
+  unsigned char* mxscale;   // e8m0 2^0 for every block of the largest shape
+  hipMalloc(&mxscale, (size_t)maxN * 8192 / 32);
+  hipMemset(mxscale, 127, (size_t)maxN * 8192 / 32);
+
   // numerics check on a small shape
   {
     const int cK = 512, cN = 64;
@@ -484,8 +490,8 @@ int main(int argc, char** argv) {
 #define RATE(F, WPB, U, NT, MT, NTL, GB, WP, SCALE, RR)                     \
   (GB / bench(skinny_gemm_kernel<F, WPB, U, NT, MT, NTL>,                   \
               (s.N + NT * 16 - 1) / (NT * 16), WPB * 64, iters, RR,         \
-              (size_t)s.N * s.K, x, WP, (const float*)SCALE, y, M, s.N,     \
-              s.K) * 1e3)
+              (size_t)s.N * s.K / F::WPACK, x, WP,                          \
+              (const typename F::scale_t*)SCALE, y, M, s.N, s.K) * 1e3)
 #define RUN1(WPB, U, NT, NTL, RR)                                           \
   RATE(Bf16Plain, WPB, U, NT, 1, NTL, gb, w, nullptr, RR)
 #define RUN(WPB, U, NT)                                                     \
@@ -543,8 +549,33 @@ int main(int argc, char** argv) {
       FP8_GEMM_CONFIGS(RUNF)
 #undef RUNF
 #undef RUNF1
-#undef RATE
     }
+    // W4A16 (Mxfp4Coal): the same pool read as packed e2m1 bytes, nt W
+    // loads, cold over R4 copies (R4 * bytes >= 1 GiB); TB/s are of the
+    // packed W plus its scales. The scales (all 2^0) are one buffer, not
+    // rotated: 1/17 of the bytes. Timing only.
+    if (M <= 16 * MXFP4_GEMM_MAX_MT) {
+      const size_t w4bytes = (size_t)s.N * s.K / 2;
+      const int R4 = (int)std::max<size_t>(
+          2, (((size_t)1 << 30) + w4bytes - 1) / w4bytes);
+      const double gb4 = (double)(w4bytes + w4bytes / 16) / 1e9;
+      printf("\n    MXFP4 R=%d", R4);
+#define RUNM1(WPB, U, NT, MT, RR)                                           \
+  RATE(Mxfp4Coal, WPB, U, NT, MT, 1, gb4, (const unsigned char*)w, mxscale, \
+       RR)
+#define RUNM(WPB, U, NT)                                                    \
+  if (s.K % (WPB * 256 * U) == 0) {                                         \
+    double h = M <= 16 ? RUNM1(WPB, U, NT, 1, 1) : RUNM1(WPB, U, NT, 2, 1); \
+    double c = M <= 16 ? RUNM1(WPB, U, NT, 1, R4)                           \
+                       : RUNM1(WPB, U, NT, 2, R4);                          \
+    printf("\n    MXFP4 w%du%dn%d  hot %5.2f | cold %5.2f TB/s (%6.1f us)",  \
+           WPB, U, NT, h, c, gb4 / c * 1e3);                                \
+  }
+      MXFP4_GEMM_CONFIGS(RUNM)
+#undef RUNM
+#undef RUNM1
+    }
+#undef RATE
     printf("\n        ");
     #define RUNC(U, NT)                                                         \
   {                                                                         \
@@ -601,6 +632,6 @@ int main(int argc, char** argv) {
     RUNC2(0, 512) RUNC2(1, 512) RUNC2(2, 512)
 #undef RUNC2
   }
-  hipFree(x); hipFree(w); hipFree(y);
+  hipFree(x); hipFree(w); hipFree(y); hipFree(wscale); hipFree(mxscale);
   return 0;
 }

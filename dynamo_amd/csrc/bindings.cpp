@@ -65,6 +65,11 @@ void fp8_skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor wq,
                      torch::Tensor scale, int64_t wpb, int64_t u, int64_t nt,
                      bool nontemporal);
 void fp8_dequant(torch::Tensor out, torch::Tensor wq, torch::Tensor scale);
+void mxfp4_skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor q,
+                       torch::Tensor scale, int64_t wpb, int64_t u,
+                       int64_t nt, bool nontemporal);
+int64_t mxfp4_gemm_max_m();
+void mxfp4_dequant(torch::Tensor out, torch::Tensor q, torch::Tensor scale);
 // moe.hip
 void moe_grouped_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                       torch::Tensor tiles);
@@ -139,8 +144,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nt") = 2, py::arg("nontemporal") = true);
   m.def("fp8_dequant", &fp8_dequant, py::arg("out"), py::arg("wq"),
         py::arg("scale"));
-  // {"bf16_plain" | "bf16_coalesced" | "fp8": [(WPB, U, NT), ...]}: what the
-  // two GEMM bindings can launch
+  // W4A16: y = x @ W_eff^T for 1 <= M <= mxfp4_gemm_max_m(), OCP MXFP4
+  // weights (q: two e2m1 codes per byte, scale: one e8m0 byte per 32 k);
+  // raises on anything the kernel does not handle - dispatch lives in
+  // ops.linear
+  m.def("mxfp4_skinny_gemm", &mxfp4_skinny_gemm, py::arg("y"), py::arg("x"),
+        py::arg("q"), py::arg("scale"), py::arg("wpb") = 1, py::arg("u") = 1,
+        py::arg("nt") = 2, py::arg("nontemporal") = true);
+  m.def("mxfp4_gemm_max_m", &mxfp4_gemm_max_m);
+  m.def("mxfp4_dequant", &mxfp4_dequant, py::arg("out"), py::arg("q"),
+        py::arg("scale"));
+  // {"bf16_plain" | "bf16_coalesced" | "fp8" | "mxfp4": [(WPB, U, NT), ...]}:
+  // what the GEMM bindings can launch
   m.def("skinny_gemm_configs", &skinny_gemm_configs);
   m.def("moe_grouped_gemm", &moe_grouped_gemm);
   m.def("moe_grouped_gemm_seg", &moe_grouped_gemm_seg);

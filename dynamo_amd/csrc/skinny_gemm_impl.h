@@ -1,15 +1,20 @@
-// Skinny-M (decode-regime) weight GEMM and fp8 weight dequantisation for
+// Skinny-M (decode-regime) weight GEMM and fp8 / mxfp4 weight dequantisation for
 // MI355X/gfx950, shared by the production binding (skinny_gemm.hip) and the
 // standalone sweep tool (benchmarks/skinny_sweep.hip), which picks
-// (WPB, U, NT) per shape. One kernel, three weight formats:
+// (WPB, U, NT) per shape. One kernel, four weight formats:
 //
 //   Bf16Plain, Bf16Coal: y[M <= 16, N] = x[M, K] @ W[N, K]^T
 //   Fp8Coal (W8A16):     y[M <= 64, N] = (x[M, K] @ bf16(Wq[N, K])^T) * scale[n]
+//   Mxfp4Coal (W4A16):   y[M <= 16 MXFP4_GEMM_MAX_MT, N] = x[M, K] @ W_eff^T
 //
-// x and y bf16, fp32 accumulate. Wq holds OCP e4m3 bytes with one fp32 scale
-// per output row of W. Every finite e4m3 code is exact in bf16, so the
-// conversion loses nothing; the scale is applied once, in fp32, in the
-// epilogue.
+// x and y bf16, fp32 accumulate. Fp8Coal: Wq holds OCP e4m3 bytes with one
+// fp32 scale per output row of W. Every finite e4m3 code is exact in bf16, so
+// the conversion loses nothing; the scale is applied once, in fp32, in the
+// epilogue. Mxfp4Coal: OCP microscaling FP4, two e2m1 codes per byte (even k
+// in the low nibble) and one e8m0 scale byte per 32 consecutive k of a row;
+// W_eff = e2m1(code) * 2^(scale - 127) is exact in bf16 (ops/mxfp4_weights.py
+// keeps the scale byte in [27, 227] so it is a normal number), the scale is
+// applied by the conversion, and there is no epilogue scale.
 //
 // At these M the GEMM is pure W streaming: every W byte is read once per call
 // by exactly one wave. mfma_f32_16x16x32_bf16 with A = x, B = W^T; per-lane
@@ -51,6 +56,17 @@
 // k = 16c + 64(s >> 1) + 8(s & 1) + 0..7 of the 128-k block, and the A
 // fragment of that step is read from the same k (16 rows x four 32 B runs:
 // full 128 B lines of x as well).
+//
+// Mxfp4Coal: Fp8Coal with half the bytes per k again. A 128 B line of a row
+// is 256 k; two instructions cover a 16-row x 256-k block = eight MFMA steps,
+// a source lane's 16 B are exactly one MX block, and ds_bpermute moves one
+// dword (8 codes = one B fragment): step s of dest lane (n, c) takes dword
+// s & 3 of load (n >> 3), lane 8(n & 7) + c + 4(s >> 2), i.e.
+// k = 32(c + 4(s >> 2)) + 8(s & 3) + 0..7 of the 256-k block. Its scale is
+// byte c + 4(s >> 2) of the 8 scale bytes of row n for the block: the dest
+// lane loads those 8 B itself per step and column tile, on the default cache
+// policy (16 lanes x 4 read the same 16 lines), and four
+// v_cvt_scalef32_pk_bf16_fp4 turn the dword into the fragment.
 //
 // NTL = 1 loads W with the non-temporal policy (global_load_dwordx4 ... nt):
 // W is read once, keeping it out of the caches' way. x stays on the default
@@ -96,6 +112,24 @@ DEVINL bf16x8 e4m3x8_to_bf16x8(int w0, int w1) {
 }
 #endif
 
+// 8 packed e2m1 codes (k in nibble order, low nibble first) times 2^(e8m0
+// byte - 127) -> 8 bf16: v_cvt_scalef32_pk_bf16_fp4 converts the two codes of
+// one byte (op_sel picks the byte) and scales by the fp32 operand, here
+// exactly the power of two.
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+#if !defined(__HIP_DEVICE_COMPILE__)
+DEVINL bf16x8 e2m1x8_to_bf16x8(unsigned int, unsigned int) { return bf16x8{}; }
+#else
+DEVINL bf16x8 e2m1x8_to_bf16x8(unsigned int w, unsigned int e8m0) {
+  const float sc = __uint_as_float(e8m0 << 23);
+  const bf16x2 f[4] = {__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 0),
+                       __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 1),
+                       __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 2),
+                       __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 3)};
+  return *reinterpret_cast<const bf16x8*>(f);
+}
+#endif
+
 // ---- weight formats --------------------------------------------------------
 // KSTEP: k per pipeline step. LOADS: W load instructions per step and column
 // tile; load h of a lane reads 16 B at row w_row(lane, h) of the tile,
@@ -105,18 +139,25 @@ DEVINL bf16x8 e4m3x8_to_bf16x8(int w0, int w1) {
 // b_frag needs of the lane. The kernel evaluates it once, ahead of the loop:
 // derived inside b_frag it is computed for the loop and again for the drain,
 // 2 more VGPRs, which took Fp8Coal <1, 1, 2, MT 4> from 3 waves/SIMD to 2.
-// SCALED: the epilogue multiplies by scale[col].
+// SCALED: the epilogue multiplies by scale[col]. WPACK: k per welem; w_k
+// counts welems.
+// BLOCK_SCALED: scale is [N, K / 32] bytes; per step and column tile the lane
+// loads the Aux (8 B: the step's 8 block scales of row lane & 15) alongside
+// W, and b_frag gets it. The other formats' Aux is empty.
+struct NoAux {};
 struct Bf16Plain {
   typedef short welem;
+  typedef float scale_t;
+  typedef NoAux Aux;
   struct Sel {};
-  static constexpr int KSTEP = 32, LOADS = 1, FRAGS = 1;
-  static constexpr bool SCALED = false;
+  static constexpr int KSTEP = 32, LOADS = 1, FRAGS = 1, WPACK = 1;
+  static constexpr bool SCALED = false, BLOCK_SCALED = false;
   static DEVINL int w_row(int lane, int) { return lane & 15; }
   static DEVINL int w_k(int lane) { return (lane >> 4) * 8; }
   static DEVINL int x_k(int lane) { return (lane >> 4) * 8; }
   static constexpr int x_step(int) { return 0; }
   static DEVINL Sel sel(int) { return {}; }
-  static DEVINL bf16x8 b_frag(int, const int4v (&r)[1], Sel) {
+  static DEVINL bf16x8 b_frag(int, const int4v (&r)[1], Sel, Aux) {
     return *reinterpret_cast<const bf16x8*>(&r[0]);
   }
 };
@@ -138,15 +179,17 @@ DEVINL int coal_take(CoalSel l, int chunk, const int4v (&r)[2], int dword) {
 
 struct Bf16Coal {
   typedef short welem;
+  typedef float scale_t;
+  typedef NoAux Aux;
   typedef CoalSel Sel;
-  static constexpr int KSTEP = 64, LOADS = 2, FRAGS = 2;
-  static constexpr bool SCALED = false;
+  static constexpr int KSTEP = 64, LOADS = 2, FRAGS = 2, WPACK = 1;
+  static constexpr bool SCALED = false, BLOCK_SCALED = false;
   static DEVINL int w_row(int lane, int h) { return coal_w_row(lane, h); }
   static DEVINL int w_k(int lane) { return (lane & 7) * 8; }
   static DEVINL int x_k(int lane) { return (lane >> 4) * 8; }
   static constexpr int x_step(int s) { return 32 * s; }
   static DEVINL Sel sel(int lane) { return coal_sel(lane); }
-  static DEVINL bf16x8 b_frag(int s, const int4v (&r)[2], Sel l) {
+  static DEVINL bf16x8 b_frag(int s, const int4v (&r)[2], Sel l, Aux) {
     int4v b;
 #pragma unroll
     for (int j = 0; j < 4; j++) b[j] = coal_take(l, s, r, j);
@@ -156,28 +199,50 @@ struct Bf16Coal {
 
 struct Fp8Coal {
   typedef unsigned char welem;
+  typedef float scale_t;
+  typedef NoAux Aux;
   typedef CoalSel Sel;
-  static constexpr int KSTEP = 128, LOADS = 2, FRAGS = 4;
-  static constexpr bool SCALED = true;
+  static constexpr int KSTEP = 128, LOADS = 2, FRAGS = 4, WPACK = 1;
+  static constexpr bool SCALED = true, BLOCK_SCALED = false;
   static DEVINL int w_row(int lane, int h) { return coal_w_row(lane, h); }
   static DEVINL int w_k(int lane) { return (lane & 7) * 16; }
   static DEVINL int x_k(int lane) { return (lane >> 4) * 16; }
   static constexpr int x_step(int s) { return 64 * (s >> 1) + 8 * (s & 1); }
   static DEVINL Sel sel(int lane) { return coal_sel(lane); }
-  static DEVINL bf16x8 b_frag(int s, const int4v (&r)[2], Sel l) {
+  static DEVINL bf16x8 b_frag(int s, const int4v (&r)[2], Sel l, Aux) {
     return e4m3x8_to_bf16x8(coal_take(l, s >> 1, r, 2 * (s & 1)),
                             coal_take(l, s >> 1, r, 2 * (s & 1) + 1));
   }
 };
 
+typedef __attribute__((ext_vector_type(2))) unsigned int uint2v;
+struct Mxfp4Coal {
+  typedef unsigned char welem;   // two e2m1 codes
+  typedef unsigned char scale_t; // e8m0, [N, K / 32]
+  typedef uint2v Aux;
+  struct Sel { CoalSel c; int shift; };
+  static constexpr int KSTEP = 256, LOADS = 2, FRAGS = 8, WPACK = 2;
+  static constexpr bool SCALED = false, BLOCK_SCALED = true;
+  static DEVINL int w_row(int lane, int h) { return coal_w_row(lane, h); }
+  static DEVINL int w_k(int lane) { return (lane & 7) * 16; }   // welems
+  static DEVINL int x_k(int lane) { return (lane >> 4) * 32; }
+  static constexpr int x_step(int s) { return 128 * (s >> 2) + 8 * (s & 3); }
+  static DEVINL Sel sel(int lane) { return {coal_sel(lane), (lane >> 4) * 8}; }
+  static DEVINL bf16x8 b_frag(int s, const int4v (&r)[2], Sel l, Aux a) {
+    return e2m1x8_to_bf16x8(coal_take(l.c, s >> 2, r, s & 3),
+                            (a[s >> 2] >> l.shift) & 0xffu);
+  }
+};
+
 // Requires K % (WPB * F::KSTEP * U) == 0, 1 <= M <= 16 MT, N >= 1. Rows >= M
 // read row 0 and tile columns >= N read column N-1 (clamped addresses);
-// neither is stored. scale is read only if F::SCALED.
+// neither is stored. scale is read only if F::SCALED ([N]) or
+// F::BLOCK_SCALED ([N, K / 32]).
 template <class F, int WPB, int U, int NT, int MT, int NTL>
 __global__ __launch_bounds__(WPB * 64) void skinny_gemm_kernel(
     const short* __restrict__ x,               // [M, K] bf16 row-major
     const typename F::welem* __restrict__ w,   // [N, K] row-major
-    const float* __restrict__ scale,           // [N]
+    const typename F::scale_t* __restrict__ scale,
     short* __restrict__ y,                     // [M, N] bf16 row-major
     int M, int N, int K) {
   const int lane = threadIdx.x & 63;
@@ -203,8 +268,17 @@ __global__ __launch_bounds__(WPB * 64) void skinny_gemm_kernel(
 #pragma unroll
     for (int h = 0; h < F::LOADS; h++) {
       const int col = n0 + t * 16 + F::w_row(lane, h);
-      wp[t][h] = w + (size_t)(col < N ? col : N - 1) * K + k0 + F::w_k(lane);
+      wp[t][h] = w + (size_t)(col < N ? col : N - 1) * (K / F::WPACK) +
+                 k0 / F::WPACK + F::w_k(lane);
     }
+  const typename F::scale_t* sp[NT];
+  if constexpr (F::BLOCK_SCALED) {
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+      const int col = n0 + t * 16 + lr;
+      sp[t] = scale + ((size_t)(col < N ? col : N - 1) * K + k0) / 32;
+    }
+  }
 
   const typename F::Sel sel = F::sel(lane);
 
@@ -216,6 +290,7 @@ __global__ __launch_bounds__(WPB * 64) void skinny_gemm_kernel(
 
   bf16x8 abuf[U][MT][F::FRAGS];
   int4v rbuf[NT][U][F::LOADS];
+  typename F::Aux auxbuf[NT][U];
   auto load_x = [&](bf16x8 (&a)[MT][F::FRAGS], int d) {
 #pragma unroll
     for (int m = 0; m < MT; m++)
@@ -224,16 +299,20 @@ __global__ __launch_bounds__(WPB * 64) void skinny_gemm_kernel(
         a[m][s] = *reinterpret_cast<const bf16x8*>(xp[m] + d * F::KSTEP +
                                                    F::x_step(s));
   };
-  auto load_w = [&](int4v (&r)[F::LOADS], int t, int d) {
+  auto load_w = [&](int4v (&r)[F::LOADS], typename F::Aux& ax, int t, int d) {
 #pragma unroll
     for (int h = 0; h < F::LOADS; h++)
-      r[h] = ldw<NTL>(wp[t][h] + d * F::KSTEP);
+      r[h] = ldw<NTL>(wp[t][h] + d * (F::KSTEP / F::WPACK));
+    if constexpr (F::BLOCK_SCALED)
+      ax = *reinterpret_cast<const typename F::Aux*>(sp[t] +
+                                                     d * (F::KSTEP / 32));
   };
   auto consume = [&](const bf16x8 (&a)[MT][F::FRAGS],
-                     const int4v (&r)[F::LOADS], f32x4 (&c)[MT]) {
+                     const int4v (&r)[F::LOADS], typename F::Aux ax,
+                     f32x4 (&c)[MT]) {
 #pragma unroll
     for (int s = 0; s < F::FRAGS; s++) {
-      const bf16x8 b = F::b_frag(s, r, sel);
+      const bf16x8 b = F::b_frag(s, r, sel, ax);
 #pragma unroll
       for (int m = 0; m < MT; m++)
         c[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m][s], b, c[m],
@@ -247,7 +326,7 @@ __global__ __launch_bounds__(WPB * 64) void skinny_gemm_kernel(
   for (int u = 0; u < U; u++) {
     load_x(abuf[u], u);
 #pragma unroll
-    for (int t = 0; t < NT; t++) load_w(rbuf[t][u], t, u);
+    for (int t = 0; t < NT; t++) load_w(rbuf[t][u], auxbuf[t][u], t, u);
   }
   for (int d = U; d < steps; d += U) {
 #pragma unroll
@@ -263,15 +342,17 @@ __global__ __launch_bounds__(WPB * 64) void skinny_gemm_kernel(
         int4v r[F::LOADS];
 #pragma unroll
         for (int h = 0; h < F::LOADS; h++) r[h] = rbuf[t][u][h];
-        load_w(rbuf[t][u], t, d + u);
-        consume(a, r, acc[t]);
+        const typename F::Aux ax = auxbuf[t][u];
+        load_w(rbuf[t][u], auxbuf[t][u], t, d + u);
+        consume(a, r, ax, acc[t]);
       }
     }
   }
 #pragma unroll
   for (int u = 0; u < U; u++)
 #pragma unroll
-    for (int t = 0; t < NT; t++) consume(abuf[u], rbuf[t][u], acc[t]);
+    for (int t = 0; t < NT; t++)
+      consume(abuf[u], rbuf[t][u], auxbuf[t][u], acc[t]);
 
   // Cross-wave reduction, one M tile at a time so the LDS footprint does
   // not grow with MT: waves 1..WPB-1 park their accumulators, wave 0 sums
@@ -352,6 +433,20 @@ __global__ __launch_bounds__(256) void fp8_dequant_kernel(
   op[1] = o[1];
 }
 
+// out[n, k] = bf16(W_eff[n, k]); one thread converts one 32-k MX block (one
+// 16 B load, one scale byte, four 16 B stores). Requires K % 32 == 0.
+__global__ __launch_bounds__(256) void mxfp4_dequant_kernel(
+    short* __restrict__ out, const unsigned char* __restrict__ q,
+    const unsigned char* __restrict__ scale, long long blocks) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= blocks) return;
+  const unsigned int e = scale[i];
+  const int4v v = *reinterpret_cast<const int4v*>(q + i * 16);
+  bf16x8* op = reinterpret_cast<bf16x8*>(out + i * 32);
+#pragma unroll
+  for (int j = 0; j < 4; j++) op[j] = e2m1x8_to_bf16x8((unsigned int)v[j], e);
+}
+
 // The (WPB, U, NT) points the sweep measures and the binding can launch, per
 // format; U counts steps of F::KSTEP k.
 #define SKINNY_GEMM_CONFIGS(X) /* Bf16Plain */                              \
@@ -367,5 +462,16 @@ __global__ __launch_bounds__(256) void fp8_dequant_kernel(
 #define FP8_GEMM_CONFIGS(X)                                                 \
   X(1, 1, 1) X(1, 1, 2) X(1, 2, 2) X(2, 1, 4) X(2, 2, 2)                     \
   X(4, 1, 2) X(4, 2, 2) X(4, 1, 4) X(8, 1, 2) X(8, 2, 2)
+
+// Mxfp4Coal, each for MT = 1..MXFP4_GEMM_MAX_MT. (1, 1, *) accept every
+// K % 256 == 0. With FRAGS = 8 the A fragments alone are 32 U MT VGPRs:
+// MT = 2 (M <= 32) is the largest at which no point of the table uses
+// scratch; at MT = 3 and 4 (8, 1, 4) spills 60 and 220 B per lane and most
+// others run 1 wave/SIMD out of AGPR copies (profiles/README.md, "MXFP4
+// weights").
+#define MXFP4_GEMM_CONFIGS(X)                                               \
+  X(1, 1, 1) X(1, 1, 2) X(1, 2, 2) X(2, 1, 2) X(2, 1, 4) X(4, 1, 2)          \
+  X(4, 1, 4) X(4, 1, 8) X(8, 1, 2) X(8, 1, 4) X(2, 1, 8)
+#define MXFP4_GEMM_MAX_MT 2
 
 }  // namespace skinny

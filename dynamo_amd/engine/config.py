@@ -142,9 +142,12 @@ class EngineConfig:
     # Storage of the dense projection weights (qkv, o, gate/up, down):
     # "bf16" keeps the compute dtype, unquantised; "fp8" stores OCP e4m3
     # with one fp32 scale per output row (W8A16: half the weight bytes per
-    # decode step, and the freed HBM goes to the KV pool); "auto" follows
-    # DYNAMO_WEIGHT_DTYPE, whose default is bf16. llama/qwen2 only.
-    weight_dtype: str = "auto"          # auto | bf16 | fp8
+    # decode step, and the freed HBM goes to the KV pool); "mxfp4" stores
+    # OCP microscaling FP4, e2m1 codes with one e8m0 scale per 32 k (W4A16:
+    # 4.25 bits per weight; every projection K must be a multiple of 32);
+    # "auto" follows DYNAMO_WEIGHT_DTYPE, whose default is bf16. llama/qwen2
+    # only.
+    weight_dtype: str = "auto"          # auto | bf16 | fp8 | mxfp4
     # waiting-queue admission policy (reference parity: kv-router
     # scheduling/policy.rs SchedulingPolicy FCFS/LCFS/WSPT):
     #   fcfs = arrival order; lcfs = newest first; wspt = shortest
@@ -187,17 +190,17 @@ class EngineConfig:
 
     @property
     def resolved_weight_dtype(self) -> str:
-        """"bf16" or "fp8": an explicit weight_dtype wins, "auto" follows
-        DYNAMO_WEIGHT_DTYPE (default bf16)."""
+        """"bf16", "fp8" or "mxfp4": an explicit weight_dtype wins, "auto"
+        follows DYNAMO_WEIGHT_DTYPE (default bf16)."""
         v = self.weight_dtype
         if v == "auto":
             from dynamo_amd import envs
             v = envs.get("DYNAMO_WEIGHT_DTYPE", "bf16") or "bf16"
             if v == "auto":
                 v = "bf16"
-        if v not in ("bf16", "fp8"):
+        if v not in ("bf16", "fp8", "mxfp4"):
             raise ValueError(
-                f"weight_dtype must be auto, bf16 or fp8, got {v!r}")
+                f"weight_dtype must be auto, bf16, fp8 or mxfp4, got {v!r}")
         return v
 
     @property

@@ -102,16 +102,17 @@ class LLMEngine:
             self.graph_runner.graphs.clear()
             self.graph_runner.dirty = True
 
-    def _refuse_on_fp8_weights(self, what: str):
-        if getattr(self.runner, "weight_dtype", "bf16") == "fp8":
+    def _refuse_on_quantised_weights(self, what: str):
+        wd = getattr(self.runner, "weight_dtype", "bf16")
+        if wd in ("fp8", "mxfp4"):
             raise ValueError(
-                f"{what} is not supported on an engine with fp8 weights "
-                "(weight_dtype=\"fp8\"): the projections are stored "
+                f"{what} is not supported on an engine with {wd} weights "
+                f"(weight_dtype=\"{wd}\"): the projections are stored "
                 "quantised")
 
     def load_lora(self, name, path=None, rank=8, alpha=16.0, seed=0,
                   activate=True):
-        self._refuse_on_fp8_weights("load_lora")
+        self._refuse_on_quantised_weights("load_lora")
         self.lora.load(name, path=path, rank=rank, alpha=alpha, seed=seed)
         if activate:
             self.lora.activate(name)
@@ -343,7 +344,7 @@ class LLMEngine:
         (modeling a policy push without checkpoint files), then invalidate
         captured graphs and flush the KV/prefix cache — cached KV computed
         under the old weights is invalid."""
-        self._refuse_on_fp8_weights("apply_weight_delta")
+        self._refuse_on_quantised_weights("apply_weight_delta")
         model = getattr(self.runner, "model", None)
         count = 0
         if model is not None:

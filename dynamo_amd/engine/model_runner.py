@@ -28,15 +28,17 @@ class ModelRunner:
         self.tp = tp or TPContext(cfg.tp_size, cfg.tp_rank)
         m = cfg.model
         self.weight_dtype = cfg.resolved_weight_dtype
-        if self.weight_dtype == "fp8":
+        if self.weight_dtype in ("fp8", "mxfp4"):
+            wd = self.weight_dtype
             if m.arch in ("opt", "mixtral"):
                 raise ValueError(
-                    f"fp8 weights are not supported for arch {m.arch!r}: "
-                    "only the llama/qwen2 dense projections have a W8A16 "
-                    "path (MoE experts and OPT layers use other kernels)")
+                    f"{wd} weights are not supported for arch {m.arch!r}: "
+                    "only the llama/qwen2 dense projections have a "
+                    "weight-only quantised path (MoE experts and OPT layers "
+                    "use other kernels)")
             if weight_pool is not None:
                 raise ValueError(
-                    "fp8 weights cannot be combined with a GMS weight pool: "
+                    f"{wd} weights cannot be combined with a GMS weight pool: "
                     "the pool shares unquantised tensors between workers")
         from dynamo_amd.models.registry import build_model
         if weight_pool is not None:
@@ -52,10 +54,13 @@ class ModelRunner:
             import logging
             logging.getLogger("dynamo_amd.engine").info(
                 "loaded %d checkpoint tensors from %s", n, m.weights_path)
+        # after the weights are final, before the KV pool is sized: the pool
+        # is sized from free memory and sees what quantising freed
         if self.weight_dtype == "fp8":
-            # after the weights are final, before the KV pool is sized: the
-            # pool is sized from free memory and sees what quantising freed
             ops.quantize_model_fp8(self.model)
+        elif self.weight_dtype == "mxfp4":
+            # ValueError if a projection's K is no multiple of 32
+            ops.quantize_model_mxfp4(self.model)
         self.hkv_local = max(1, m.num_kv_heads // self.tp.size)
         self.hq_local = m.num_q_heads // self.tp.size
 

@@ -44,7 +44,8 @@ ENV_VARS = {
     "DYNAMO_WEIGHT_DTYPE":
         "what EngineConfig.weight_dtype=\"auto\" resolves to: bf16 (default; "
         "the compute dtype, unquantised) | fp8 (e4m3 projection weights, "
-        "W8A16)",
+        "W8A16) | mxfp4 (OCP microscaling FP4 projection weights: e2m1 codes "
+        "with one e8m0 scale per 32 k, W4A16)",
     "DYNAMO_MOE_BMM": "0 = grouped-kernel MoE decode instead of padded bmm",
     "DYNAMO_MOE_MFMA": "0 = VALU grouped MoE GEMM",
     "DYNAMO_MOE_GRAPHS": "0 = exclude MoE layers from hipGraph capture",

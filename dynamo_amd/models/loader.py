@@ -211,10 +211,11 @@ def export_hf(model, path: str):
     """Inverse mapping (tp=1 only): write this model's weights as an
     HF-named safetensors checkpoint + config.json. Used by the round-trip
     test and as a conversion utility."""
-    if getattr(model, "weight_dtype", None) == "fp8":
+    wd = getattr(model, "weight_dtype", None)
+    if wd in ("fp8", "mxfp4"):
         raise ValueError("export_hf: the model's projections are stored as "
-                         "fp8 (weight_dtype=\"fp8\"); export an unquantised "
-                         "model")
+                         f"{wd} (weight_dtype=\"{wd}\"); export an "
+                         "unquantised model")
     from safetensors.torch import save_file
     cfg = model.cfg
     assert model.tp.size == 1, "export is tp=1 only"

@@ -8,9 +8,11 @@ from __future__ import annotations
 
 import torch
 
-from . import fp8_weights, torch_ref
+from . import fp8_weights, mxfp4_weights, torch_ref
 from .fp8_weights import (Fp8Weight, quantize_fp8_rowwise,  # re-export
                           quantize_model_fp8)
+from .mxfp4_weights import (Mxfp4Weight, quantize_mxfp4,  # re-export
+                            quantize_model_mxfp4)
 from .torch_ref import make_cos_sin_cache  # re-export
 
 _hip_mod = None
@@ -126,17 +128,55 @@ FP8_GEMM_SHAPES: dict = {
 FP8_GEMM_MAX_M = 64
 
 
+def _quant_gemm_config(M, N, K, kstep, max_m, shapes, split_k, default):
+    """The (WPB, U, NT) of a quantised-weight GEMM whose steps are kstep k:
+    the shape's table entry (first for M <= 16, second above), else split_k,
+    else, where K does not allow that, default. None if the kernel does not
+    take the shape."""
+    if not (1 <= M <= max_m and K >= kstep and K % kstep == 0
+            and N >= 16 and N % 16 == 0):
+        return None
+    entry = shapes.get((N, K))
+    cfg = entry[0 if M <= 16 else 1] if entry else split_k
+    if K % (cfg[0] * kstep * cfg[1]):
+        cfg = default
+    return cfg
+
+
+def _quant_linear_path(x, w, dequant_k, gemm_config):
+    """("kernel", cfg) | ("dequant", None) | ("torch", None) for linear(x, w)
+    with a quantised weight holder w whose dequantise kernel needs
+    K % dequant_k == 0."""
+    N, K = w.shape
+    if not x.is_cuda:
+        return "torch", None
+    if x.dtype != torch.bfloat16 or K % dequant_k or x.shape[-1] != K:
+        return "torch", None
+    if x.dim() == 2 and x.is_contiguous() and x.data_ptr() % 16 == 0:
+        cfg = gemm_config(x.shape[0], N, K)
+        if cfg is not None:
+            return "kernel", cfg
+    return "dequant", None
+
+
+def _linear_quant(x, w, path, cfg, gemm: str, dequant: str):
+    """linear(x, w) on `path`; gemm and dequant name the format's bindings."""
+    if path == "kernel":
+        y = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
+        getattr(hip(), gemm)(y, x, w.q, w.scale, *cfg, True)
+        return y
+    if path == "dequant":
+        w_eff = fp8_weights.scratch_view(w)
+        getattr(hip(), dequant)(w_eff, w.q, w.scale)
+        return torch.nn.functional.linear(x, w_eff)
+    return torch.nn.functional.linear(x, w.effective(x.dtype))
+
+
 def fp8_gemm_config(M: int, N: int, K: int):
     """The (WPB, U, NT) fp8_skinny_gemm runs an [M, K] x [N, K]^T call at, or
     None if the kernel does not take the shape."""
-    if not (1 <= M <= FP8_GEMM_MAX_M and K >= 128 and K % 128 == 0
-            and N >= 16 and N % 16 == 0):
-        return None
-    entry = FP8_GEMM_SHAPES.get((N, K))
-    cfg = entry[0 if M <= 16 else 1] if entry else FP8_GEMM_SPLIT_K
-    if K % (cfg[0] * 128 * cfg[1]):
-        cfg = FP8_GEMM_DEFAULT
-    return cfg
+    return _quant_gemm_config(M, N, K, 128, FP8_GEMM_MAX_M, FP8_GEMM_SHAPES,
+                              FP8_GEMM_SPLIT_K, FP8_GEMM_DEFAULT)
 
 
 def fp8_linear_path(x: torch.Tensor, w: Fp8Weight):
@@ -145,37 +185,77 @@ def fp8_linear_path(x: torch.Tensor, w: Fp8Weight):
     scratch buffer + the library GEMM, ("torch", None) for F.linear(x, W_eff)
     with W_eff formed by torch (CPU, or a GPU call fp8_dequant cannot
     serve)."""
-    N, K = w.shape
-    if not x.is_cuda:
-        return "torch", None
-    if x.dtype != torch.bfloat16 or K % 16 or x.shape[-1] != K:
-        return "torch", None
-    if x.dim() == 2 and x.is_contiguous() and x.data_ptr() % 16 == 0:
-        cfg = fp8_gemm_config(x.shape[0], N, K)
-        if cfg is not None:
-            return "kernel", cfg
-    return "dequant", None
+    return _quant_linear_path(x, w, 16, fp8_gemm_config)
 
 
 def _linear_fp8(x: torch.Tensor, w: Fp8Weight) -> torch.Tensor:
-    path, cfg = fp8_linear_path(x, w)
-    if path == "kernel":
-        y = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
-        hip().fp8_skinny_gemm(y, x, w.q, w.scale, *cfg, True)
-        return y
-    if path == "dequant":
-        w_eff = fp8_weights.scratch_view(w)
-        hip().fp8_dequant(w_eff, w.q, w.scale)
-        return torch.nn.functional.linear(x, w_eff)
-    return torch.nn.functional.linear(x, w.effective(x.dtype))
+    return _linear_quant(x, w, *fp8_linear_path(x, w), "fp8_skinny_gemm",
+                         "fp8_dequant")
+
+
+# --------------------------------------------------------------------------
+# MXFP4 (e2m1 + e8m0) weights, W4A16 (ops/mxfp4_weights.py, the Mxfp4Coal
+# format of csrc/skinny_gemm_impl.h). (WPB, U, NT) points of mxfp4_skinny_gemm
+# the binding can launch; it needs K % (WPB * 256 * U) == 0. A copy of the
+# header's MXFP4_GEMM_CONFIGS that tests can read without the extension; they
+# check it against hip().skinny_gemm_configs(). Non-temporal W loads
+# throughout.
+MXFP4_GEMM_CONFIGS: tuple = (
+    (1, 1, 1), (1, 1, 2), (1, 2, 2), (2, 1, 2), (2, 1, 4), (4, 1, 2),
+    (4, 1, 4), (4, 1, 8), (8, 1, 2), (8, 1, 4), (2, 1, 8),
+)
+# The default configuration accepts every K % 256 == 0; a shape outside the
+# table takes the 4-wave K split when K allows, as for fp8 (1.4-2.1x the bf16
+# dispatch on all four 70B layer shapes at M = 16, where the default ranges
+# from 0.9x to 2.1x).
+MXFP4_GEMM_DEFAULT: tuple = (1, 1, 2)
+MXFP4_GEMM_SPLIT_K: tuple = (4, 1, 2)
+# (N, K) -> ((WPB, U, NT) for M <= 16, (WPB, U, NT) for 16 < M <= 32) for the
+# llama-3-70b layer shapes: the cold-sweep winners at M = 16 and M = 32
+# (kernel_bench.py --which mxfp4sweep; profiles/README.md, "MXFP4 weights")
+MXFP4_GEMM_SHAPES: dict = {
+    (10240, 8192): ((4, 1, 4), (8, 1, 4)),    # qkv
+    (8192, 8192): ((4, 1, 2), (4, 1, 2)),     # o
+    (57344, 8192): ((2, 1, 8), (2, 1, 8)),    # gate/up
+    (8192, 28672): ((4, 1, 2), (4, 1, 2)),    # down
+}
+# the largest M at which no shipped instantiation uses scratch memory
+# (16 * MXFP4_GEMM_MAX_MT of the header); larger M takes the dequantise path
+MXFP4_GEMM_MAX_M = 32
+
+
+def mxfp4_gemm_config(M: int, N: int, K: int):
+    """The (WPB, U, NT) mxfp4_skinny_gemm runs an [M, K] x [N, K]^T call at,
+    or None if the kernel does not take the shape."""
+    return _quant_gemm_config(M, N, K, 256, MXFP4_GEMM_MAX_M,
+                              MXFP4_GEMM_SHAPES, MXFP4_GEMM_SPLIT_K,
+                              MXFP4_GEMM_DEFAULT)
+
+
+def mxfp4_linear_path(x: torch.Tensor, w: Mxfp4Weight):
+    """Where linear(x, w) runs for an Mxfp4Weight: ("kernel", (WPB, U, NT))
+    for the in-tree W4A16 kernel, ("dequant", None) for mxfp4_dequant into
+    the scratch buffer + the library GEMM, ("torch", None) for
+    F.linear(x, W_eff) with W_eff formed by torch (CPU, or x not bf16)."""
+    if w.q.data_ptr() % 16 or w.scale.data_ptr() % 8:
+        return _quant_linear_path(x, w, 32, lambda M, N, K: None)
+    return _quant_linear_path(x, w, 32, mxfp4_gemm_config)
+
+
+def _linear_mxfp4(x: torch.Tensor, w: Mxfp4Weight) -> torch.Tensor:
+    return _linear_quant(x, w, *mxfp4_linear_path(x, w), "mxfp4_skinny_gemm",
+                         "mxfp4_dequant")
 
 
 def linear(x: torch.Tensor, w) -> torch.Tensor:
     """x @ w^T. Decode-regime calls (M <= 16) on a shipped (N, K) take the
     in-tree weight-streaming kernel; every other call is F.linear. An
-    Fp8Weight goes through fp8_linear_path."""
+    Fp8Weight goes through fp8_linear_path, an Mxfp4Weight through
+    mxfp4_linear_path."""
     if isinstance(w, Fp8Weight):
         return _linear_fp8(x, w)
+    if isinstance(w, Mxfp4Weight):
+        return _linear_mxfp4(x, w)
     cfg = skinny_gemm_config(x, w)
     if cfg is None:
         return torch.nn.functional.linear(x, w)

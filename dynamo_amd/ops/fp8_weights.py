@@ -85,10 +85,13 @@ def reserve_scratch(device, numel: int) -> None:
                                        device=device)
 
 
-def scratch_view(w: Fp8Weight) -> torch.Tensor:
-    n = w.q.numel()
-    reserve_scratch(w.q.device, n)
-    return _scratch[w.q.device][:n].view(w.q.shape)
+def scratch_view(w) -> torch.Tensor:
+    """A bf16 [N, K] view of the device's scratch buffer for the quantised
+    weight holder w (an Fp8Weight or an Mxfp4Weight) to be dequantised
+    into."""
+    N, K = w.shape
+    reserve_scratch(w.q.device, N * K)
+    return _scratch[w.q.device][:N * K].view(N, K)
 
 
 PROJECTIONS = (("attn", "wqkv"), ("attn", "wo"),

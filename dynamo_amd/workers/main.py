@@ -46,10 +46,12 @@ def build_parser():
                    help="fp8 stores the paged KV cache as OCP e4m3 "
                         "(half the decode HBM bytes; GPU only)")
     p.add_argument("--weight-dtype", default="auto",
-                   choices=["auto", "bf16", "fp8"],
+                   choices=["auto", "bf16", "fp8", "mxfp4"],
                    help="fp8 stores the dense projection weights as OCP e4m3 "
-                        "with per-row scales (W8A16; llama/qwen2 only); auto "
-                        "follows DYNAMO_WEIGHT_DTYPE (default bf16)")
+                        "with per-row scales (W8A16), mxfp4 as OCP "
+                        "microscaling FP4 (e2m1 with one e8m0 scale per 32 k, "
+                        "W4A16); llama/qwen2 only; auto follows "
+                        "DYNAMO_WEIGHT_DTYPE (default bf16)")
     p.add_argument("--kv-v-layout", default="auto",
                    choices=["auto", "never"],
                    help="V-page layout: auto = d-major on GPU when supported")
