@@ -304,6 +304,57 @@ def _bench_mxfp4_gemm(name, x, ws, y, t_bf16, sweep):
               f"({t_bf16/t:4.2f}x the bf16 dispatch)")
 
 
+def bench_lora(T=16, R=64):
+    """The gathered LoRA kernel pair (csrc/lora.hip) at the four llama-3-70b
+    projection shapes, cache-cold: launch i reads copy i % C of a 16-slot
+    bank, C * bytes(bank) >= 1 GiB. Rank 16 and rank 64 in R = 64 slots, with
+    1, 4 and 16 distinct adapters among the T rows. GB/s are of the bytes
+    that must move: distinct adapters * rank * (K + N) * 2 B."""
+    S = 16
+    for name, N, K in (("qkv", 10240, 8192), ("o", 8192, 8192),
+                       ("gateup", 57344, 8192), ("down", 8192, 28672)):
+        bank_bytes = S * R * (K + N) * 2
+        C = max(2, -(-(1 << 30) // bank_bytes))
+        As = [torch.randn(S, R, K, dtype=torch.bfloat16, device="cuda") * 0.02
+              for _ in range(C)]
+        Bs = [torch.randn(S, N, R, dtype=torch.bfloat16, device="cuda") * 0.02
+              for _ in range(C)]
+        x = torch.randn(T, K, dtype=torch.bfloat16, device="cuda")
+        y = torch.randn(T, N, dtype=torch.bfloat16, device="cuda")
+        t = torch.empty(T, R, dtype=torch.float32, device="cuda")
+        scales = torch.ones(S, device="cuda")
+        for rank in (16, 64):
+            ranks = torch.full((S,), rank, dtype=torch.int32, device="cuda")
+            for distinct in (1, 4, 16):
+                slots = (torch.arange(T, device="cuda") % distinct).to(
+                    torch.int32)
+                i = [0]
+
+                def shrink():
+                    i[0] += 1
+                    ops.lora_shrink(t, x, As[i[0] % C], slots, ranks)
+
+                def expand():
+                    i[0] += 1
+                    ops.lora_expand_add(y, t, Bs[i[0] % C], slots, ranks,
+                                        scales)
+
+                def both():
+                    shrink()
+                    expand()
+
+                ts = [min(timeit(f, iters=24) for _ in range(3))
+                      for f in (shrink, expand, both)]
+                gbs = [distinct * rank * n * 2 / 1e9 for n in (K, N, K + N)]
+                row = " | ".join(
+                    f"{k} {tt*1e6:6.1f} us {gb/tt:6.0f} GB/s"
+                    for k, tt, gb in zip(("shrink", "expand", "pair"), ts,
+                                         gbs))
+                print(f"lora cold {name:7s}[{T}x{K}x{N}] C={C} rank {rank:2d} "
+                      f"adapters {distinct:2d}: {row}")
+        del As, Bs
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--which", default="all")
@@ -341,6 +392,8 @@ if __name__ == "__main__":
         bench_gemm(M=8192)
         bench_skinny_gemm()
         bench_skinny_gemm(M=64)
+    if w in ("all", "lora"):
+        bench_lora()
     if w == "fp8sweep":
         # every launchable W8A16 configuration per shape: picks
         # ops.FP8_GEMM_SHAPES

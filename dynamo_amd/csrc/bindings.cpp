@@ -70,6 +70,12 @@ void mxfp4_skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor q,
                        int64_t nt, bool nontemporal);
 int64_t mxfp4_gemm_max_m();
 void mxfp4_dequant(torch::Tensor out, torch::Tensor q, torch::Tensor scale);
+// lora.hip
+void lora_shrink(torch::Tensor t, torch::Tensor x, torch::Tensor A_bank,
+                 torch::Tensor slots, torch::Tensor ranks);
+void lora_expand_add(torch::Tensor y, torch::Tensor t, torch::Tensor B_bank,
+                     torch::Tensor slots, torch::Tensor ranks,
+                     torch::Tensor scales);
 // moe.hip
 void moe_grouped_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                       torch::Tensor tiles);
@@ -157,6 +163,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // {"bf16_plain" | "bf16_coalesced" | "fp8" | "mxfp4": [(WPB, U, NT), ...]}:
   // what the GEMM bindings can launch
   m.def("skinny_gemm_configs", &skinny_gemm_configs);
+  // batched LoRA: each row i takes the adapter in bank slot slots[i] (a
+  // device tensor; < 0 = none), so one captured graph serves any adapter mix.
+  // t[i, r] = x[i] . A_bank[s, r] and y[i] += scales[s] * t[i] @ B_bank[s]^T
+  // over r < ranks[s]; raises on K, N or R % 8 != 0, misaligned or
+  // non-contiguous tensors
+  m.def("lora_shrink", &lora_shrink, py::arg("t"), py::arg("x"),
+        py::arg("A_bank"), py::arg("slots"), py::arg("ranks"));
+  m.def("lora_expand_add", &lora_expand_add, py::arg("y"), py::arg("t"),
+        py::arg("B_bank"), py::arg("slots"), py::arg("ranks"),
+        py::arg("scales"));
   m.def("moe_grouped_gemm", &moe_grouped_gemm);
   m.def("moe_grouped_gemm_seg", &moe_grouped_gemm_seg);
   m.def("topk_gating", &topk_gating);

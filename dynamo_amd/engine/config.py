@@ -148,6 +148,14 @@ class EngineConfig:
     # "auto" follows DYNAMO_WEIGHT_DTYPE, whose default is bf16. llama/qwen2
     # only.
     weight_dtype: str = "auto"          # auto | bf16 | fp8 | mxfp4
+    # Per-request LoRA: max_loras > 0 allocates an adapter bank of that many
+    # slots (each up to max_lora_rank, a multiple of 8; fused PEFT block
+    # forms - 3r for qkv, 2r for gate/up - count against it) before the KV
+    # pool is sized, and requests may then name a loaded adapter. 0 keeps
+    # engine-level activation (dynamo_amd/lora). llama/qwen2 with
+    # unquantised weights only.
+    max_loras: int = 0
+    max_lora_rank: int = 64
     # waiting-queue admission policy (reference parity: kv-router
     # scheduling/policy.rs SchedulingPolicy FCFS/LCFS/WSPT):
     #   fcfs = arrival order; lcfs = newest first; wspt = shortest
@@ -202,6 +210,31 @@ class EngineConfig:
             raise ValueError(
                 f"weight_dtype must be auto, bf16, fp8 or mxfp4, got {v!r}")
         return v
+
+    def check_lora_bank(self, weight_pool=None) -> None:
+        """ValueError if this configuration cannot carry an adapter bank."""
+        if self.max_loras < 0:
+            raise ValueError(f"max_loras must be >= 0, got {self.max_loras}")
+        if self.max_loras == 0:
+            return
+        if self.max_lora_rank < 8 or self.max_lora_rank % 8:
+            raise ValueError(
+                "max_lora_rank must be a positive multiple of 8, got "
+                f"{self.max_lora_rank}")
+        if self.model.arch not in ("llama", "qwen2"):
+            raise ValueError(
+                f"max_loras > 0 is not supported for arch "
+                f"{self.model.arch!r}: only the llama/qwen2 dense "
+                "projections apply per-request adapters")
+        wd = self.resolved_weight_dtype
+        if wd != "bf16":
+            raise ValueError(
+                f"max_loras > 0 cannot be combined with {wd} weights "
+                f"(weight_dtype=\"{wd}\"): adapters on a quantised base are "
+                "not supported")
+        if weight_pool is not None:
+            raise ValueError(
+                "max_loras > 0 cannot be combined with a GMS weight pool")
 
     @property
     def kv_torch_dtype(self):

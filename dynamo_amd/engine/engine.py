@@ -89,7 +89,13 @@ class LLMEngine:
         self._puller = None   # disagg decode-side KvPuller (lazy)
         self._last_weight_delta_count = 0
 
-    # -- LoRA (engine-level activation; see dynamo_amd/lora) -----------
+    # -- LoRA (see dynamo_amd/lora): with an adapter bank (max_loras > 0)
+    # requests name their adapter; without one, one adapter is active for
+    # the whole engine ---------------------------------------------------
+    @property
+    def lora_bank(self):
+        return getattr(self.runner, "lora_bank", None)
+
     @property
     def lora(self):
         if self._lora is None and hasattr(self.runner, "model"):
@@ -110,28 +116,61 @@ class LLMEngine:
                 f"(weight_dtype=\"{wd}\"): the projections are stored "
                 "quantised")
 
+    def _refuse_lora_in_use(self, name: str, what: str):
+        if any(r.lora == name and r.state is not ReqState.FINISHED
+               for r in self.requests.values()):
+            raise ValueError(
+                f"cannot {what} LoRA {name!r}: a live request uses it")
+
     def load_lora(self, name, path=None, rank=8, alpha=16.0, seed=0,
                   activate=True):
         self._refuse_on_quantised_weights("load_lora")
+        if self.lora_bank is not None:
+            # into a bank slot: no engine-wide activation (`activate` has no
+            # meaning here), and captured graphs stay valid
+            self._refuse_lora_in_use(name, "reload")
+            self.lora_bank.load(name, path=path, rank=rank, alpha=alpha,
+                                seed=seed)
+            return
         self.lora.load(name, path=path, rank=rank, alpha=alpha, seed=seed)
         if activate:
             self.lora.activate(name)
             self._invalidate_graphs()
 
     def unload_lora(self, name):
+        if self.lora_bank is not None:
+            self._refuse_lora_in_use(name, "unload")
+            self.lora_bank.unload(name)
+            return
         self.lora.unload(name)
         self._invalidate_graphs()
 
     def list_loras(self):
+        if self.lora_bank is not None:
+            return self.lora_bank.list()
         return [] if self._lora is None else self._lora.list()
 
     # ------------------------------------------------------------------
     def add_request(self, req_id: str, prompt_tokens: List[int],
                     sampling: SamplingParams | None = None,
-                    prompt_embeds=None) -> Request:
+                    prompt_embeds=None, lora: Optional[str] = None
+                    ) -> Request:
+        slot = -1
+        if lora is not None:
+            bank = self.lora_bank
+            if bank is None:
+                raise ValueError(
+                    f"request {req_id!r} names LoRA adapter {lora!r}, but "
+                    "this engine has no adapter bank (max_loras == 0)")
+            if lora not in bank.slot_of:
+                raise ValueError(
+                    f"request {req_id!r} names LoRA adapter {lora!r}, which "
+                    f"is not loaded (loaded: {bank.list()})")
+            slot = bank.slot(lora)
         if prompt_embeds is not None and not prompt_tokens:
             prompt_tokens = [0] * prompt_embeds.shape[0]
         req = Request(req_id, prompt_tokens, sampling or SamplingParams())
+        req.lora, req.lora_slot = lora, slot
         req.prompt_embeds = prompt_embeds
         self.requests[req_id] = req
         self.scheduler.add_request(req)

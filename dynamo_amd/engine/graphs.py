@@ -43,7 +43,14 @@ class GraphRunner:
                                       device=dev)
         V = cfg.model.vocab_size
         self.logits = torch.empty(B, V, dtype=torch.float32, device=dev)
-        self.graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        # batched LoRA: the adapter-bank slot of every row (-1 = none, pad
+        # rows included). The kernels read it on the device, so a batch whose
+        # adapter mix changes refills it and replays the same graph.
+        self.lora_slots = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self.has_lora = False
+        # (bucket, has_lora) -> graph: a batch with no adapter replays a
+        # graph without the LoRA kernels and pays nothing
+        self.graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self._graph_pool = None
         # current batch composition
         self.reqs: List[Request] = []
@@ -51,8 +58,10 @@ class GraphRunner:
         self._first_after_rebuild = True
 
     # ------------------------------------------------------------------
-    def _meta(self, bc: int) -> AttnMetadata:
+    def _meta(self, bc: int, has_lora: bool = False) -> AttnMetadata:
         return AttnMetadata(
+            lora_slots=self.lora_slots[:bc] if has_lora else None,
+            lora_decode_rows=bc if has_lora else 0,
             slot_mapping=self.slot_mapping[:bc],
             positions=self.positions[:bc],
             num_decode=bc,
@@ -64,10 +73,10 @@ class GraphRunner:
         )
 
     @torch.inference_mode()
-    def _capture(self, bc: int):
+    def _capture(self, bc: int, has_lora: bool = False):
         model = self.runner.model
         kv_pool = self.runner.kv_pool
-        meta = self._meta(bc)
+        meta = self._meta(bc, has_lora)
         torch.cuda.synchronize()
         # warm up the exact op sequence on a side stream first
         s = torch.cuda.Stream()
@@ -82,7 +91,7 @@ class GraphRunner:
             self.logits[:bc] = model.compute_logits(h)
         if self._graph_pool is None:
             self._graph_pool = g.pool()
-        self.graphs[bc] = g
+        self.graphs[(bc, has_lora)] = g
 
     def _bucket(self, n: int) -> int:
         for b in BUCKETS:
@@ -110,6 +119,14 @@ class GraphRunner:
                                              dtype=torch.int32))
         self.slot_mapping[:n].copy_(torch.tensor(slots, dtype=torch.int64))
         self.page_table[:n].copy_(pt)
+        slots_l = [r.lora_slot for r in reqs]
+        has_lora = any(s >= 0 for s in slots_l)
+        if has_lora or self.has_lora:
+            self.lora_slots.fill_(-1)
+            if has_lora:
+                self.lora_slots[:n].copy_(
+                    torch.tensor(slots_l, dtype=torch.int32))
+        self.has_lora = has_lora
         # pad rows: ctx 0 disables attention; slot -1 skips kv append
         if n < self.max_batch:
             self.ctx_lens[n:].fill_(0)
@@ -146,12 +163,13 @@ class GraphRunner:
         if not self.use_graphs:
             # persistent-buffer eager path (TP ranks: RCCL-in-graph capture
             # is not exercised; MoE: host-side tile lists aren't capturable)
-            meta = self._meta(bc)
+            meta = self._meta(bc, self.has_lora)
             h = self.runner.model.forward(self.input_ids[:bc],
                                           self.runner.kv_pool, meta)
             self.logits[:bc] = self.runner.model.compute_logits(h)
             return self.logits[:n]
-        if bc not in self.graphs:
-            self._capture(bc)
-        self.graphs[bc].replay()
+        key = (bc, self.has_lora)
+        if key not in self.graphs:
+            self._capture(bc, self.has_lora)
+        self.graphs[key].replay()
         return self.logits[:n]

@@ -40,6 +40,7 @@ class ModelRunner:
                 raise ValueError(
                     f"{wd} weights cannot be combined with a GMS weight pool: "
                     "the pool shares unquantised tensors between workers")
+        cfg.check_lora_bank(weight_pool)
         from dynamo_amd.models.registry import build_model
         if weight_pool is not None:
             from dynamo_amd.gms import weight_allocator
@@ -61,6 +62,12 @@ class ModelRunner:
         elif self.weight_dtype == "mxfp4":
             # ValueError if a projection's K is no multiple of 32
             ops.quantize_model_mxfp4(self.model)
+        # the adapter bank too is allocated before the KV pool is sized
+        self.lora_bank = None
+        if cfg.max_loras > 0:
+            from dynamo_amd.lora import LoRABank
+            self.lora_bank = LoRABank(self.model, cfg.max_loras,
+                                      cfg.max_lora_rank)
         self.hkv_local = max(1, m.num_kv_heads // self.tp.size)
         self.hq_local = m.num_q_heads // self.tp.size
 
@@ -103,6 +110,10 @@ class ModelRunner:
         positions: List[int] = []
         slots: List[int] = []
         logits_rows: List[int] = []
+        # batched LoRA: the bank slot of every row, and the prefill chunks
+        # that run under an adapter
+        lora_slots: List[int] = []
+        lora_prefill: List[tuple] = []
 
         # ---- decode part ----
         nd = len(sched.decodes)
@@ -117,6 +128,8 @@ class ModelRunner:
             dec_tables.append(pages)
             dec_ctx.append(pos + 1)
             logits_rows.append(i)
+            lora_slots.append(r.lora_slot)
+        lora_decode = any(s >= 0 for s in lora_slots)
 
         # ---- prefill part ----
         pf_tables, q_start, q_len, ctx_len = [], [], [], []
@@ -148,6 +161,9 @@ class ModelRunner:
                         base = nd + qpos + (lo - nc)
                         embeds_rows.extend(range(base, base + hi - lo))
                         embeds_parts.append(emb[lo - off:hi - off])
+            lora_slots.extend([r.lora_slot] * n)
+            if r.lora_slot >= 0:
+                lora_prefill.append((nd + qpos, n, r.lora_slot))
             pf_tables.append(r.kv.pages)
             q_start.append(qpos)
             q_len.append(n)
@@ -184,6 +200,11 @@ class ModelRunner:
             logits_rows=torch.tensor(logits_rows, dtype=torch.int64).to(dev, non_blocking=True),
             v_transposed=self.v_transposed,
         )
+        if lora_decode or lora_prefill:
+            meta.lora_slots = torch.tensor(
+                lora_slots, dtype=torch.int32).to(dev, non_blocking=True)
+            meta.lora_decode_rows = nd if lora_decode else 0
+            meta.lora_prefill = lora_prefill
         if embeds_rows:
             meta.embeds_rows = torch.tensor(embeds_rows, dtype=torch.int64,
                                             device=dev)

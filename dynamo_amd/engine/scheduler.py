@@ -14,6 +14,7 @@ from dataclasses import dataclass, field
 from enum import Enum
 from typing import Dict, List, Optional
 
+from dynamo_amd.lora import lora_block_salt
 from .config import EngineConfig
 from .kv_cache import PageAllocator, SequenceKV
 
@@ -74,6 +75,10 @@ class Request:
         # of token-table embeddings (reference: preprocessor.rs:2248 media
         # + encode-worker embeddings spliced into the P/D request)
         self.embed_spans = None
+        # per-request LoRA adapter (EngineConfig.max_loras > 0): its name and
+        # its slot in the engine's adapter bank; None / -1 = base model
+        self.lora: Optional[str] = None
+        self.lora_slot = -1
 
     @property
     def has_embeds(self) -> bool:
@@ -212,7 +217,8 @@ class Scheduler:
                and len(self.running) < self.cfg.max_num_seqs):
             req = self.waiting[0]
             if req.kv is None:
-                req.kv = SequenceKV(self.alloc, self.cfg.block_salt)
+                req.kv = SequenceKV(
+                    self.alloc, lora_block_salt(self.cfg.block_salt, req.lora))
                 if (self.cfg.enable_prefix_caching and not req.prefill_result
                         and not req.has_embeds):
                     req.num_computed = req.kv.match_prefix(req.all_tokens)

@@ -41,6 +41,12 @@ ENV_VARS = {
     "DYNAMO_SKINNY_GEMM":
         "0 = every decode weight GEMM on hipBLASLt (default: the in-tree "
         "skinny-M kernel on the shapes in ops.SKINNY_GEMM_SHAPES)",
+    "DYNAMO_MAX_LORAS":
+        "default of the worker's --max-loras: adapter-bank slots for "
+        "per-request LoRA (default 0 = engine-level activation only)",
+    "DYNAMO_MAX_LORA_RANK":
+        "default of the worker's --max-lora-rank: the largest (fused block "
+        "form) adapter rank a bank slot holds, a multiple of 8 (default 64)",
     "DYNAMO_WEIGHT_DTYPE":
         "what EngineConfig.weight_dtype=\"auto\" resolves to: bf16 (default; "
         "the compute dtype, unquantised) | fp8 (e4m3 projection weights, "

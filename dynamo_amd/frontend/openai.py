@@ -182,7 +182,11 @@ def build_app(manager: ModelManager,
             {"id": name, "object": "model", "owned_by": "dynamo_amd",
              "created": int(e.card.get("registered_at", time.time()))
              if isinstance(e.card, dict) else int(time.time())}
-            for name, e in manager.models.items()]}
+            for name, e in manager.models.items()] + [
+            # LoRA adapters the workers list: served under their own name
+            {"id": lo, "object": "model", "owned_by": "dynamo_amd",
+             "created": int(time.time()), "parent": parent}
+            for lo, parent in sorted(manager.adapters().items())]}
 
     async def _run(entry, token_ids, req, rid,
                    session_id=None, extra=None) -> AsyncIterator[dict]:
@@ -370,9 +374,15 @@ def build_app(manager: ModelManager,
 
     def _entry_or_404(model):
         try:
-            return manager.get(model)
+            entry = manager.get(model)
         except KeyError as e:
             raise HTTPException(404, str(e))
+        if (entry.lora and entry.prefill_router is not None
+                and entry.prefill_router.has_prefill_pool()):
+            raise HTTPException(
+                400, f"LoRA adapter {entry.lora!r}: adapter requests are "
+                     "not supported with a prefill pool yet")
+        return entry
 
     # -- OpenAI Responses API (openai.rs:4158 handler_responses) --------
     @app.post("/v1/responses")

@@ -36,6 +36,10 @@ class ModelEntry:
     tokenizer: object = None
     templater: ChatTemplater = None
     migration_limit: int = 3
+    # a LoRA adapter served as a model of its own (ModelManager.get): the
+    # base entry's router/tokenizer under the adapter's name
+    lora: Optional[str] = None
+    parent: Optional[str] = None
 
 
 class ModelManager:
@@ -176,9 +180,32 @@ class ModelManager:
         return int(insts[0].metadata.get("tokens_per_image", 0)) if insts else 0
 
     # ------------------------------------------------------------------
+    def _lora_instances(self, entry: ModelEntry, lora: str) -> set:
+        """Ids of the entry's live workers that list the adapter."""
+        return {i.instance_id for i in entry.router.client.instances()
+                if lora in ((i.metadata or {}).get("loras") or [])}
+
+    def adapters(self) -> Dict[str, str]:
+        """{adapter name: base model name} over every live worker's
+        published `loras` metadata."""
+        out: Dict[str, str] = {}
+        for name, e in self.models.items():
+            for i in e.router.client.instances():
+                for lo in (i.metadata or {}).get("loras") or []:
+                    if lo not in self.models:
+                        out.setdefault(lo, name)
+        return out
+
     def get(self, model: str) -> ModelEntry:
         if model in self.models:
             return self.models[model]
+        # a model that equals an adapter name: the base model's entry plus
+        # the adapter, which generate_tokens puts into the payload
+        parent = self.adapters().get(model) if model else None
+        if parent is not None:
+            import dataclasses
+            return dataclasses.replace(self.models[parent], name=model,
+                                       lora=model, parent=parent)
         if len(self.models) == 1:
             return next(iter(self.models.values()))
         raise KeyError(f"model {model!r} not found; have {list(self.models)}")
@@ -210,6 +237,16 @@ class ModelManager:
             }
             if extra:
                 payload.update(extra)
+            allowed = None
+            if entry.lora:
+                if (entry.prefill_router is not None
+                        and entry.prefill_router.has_prefill_pool()):
+                    raise ValueError(
+                        f"LoRA adapter {entry.lora!r}: adapter requests are "
+                        "not supported with a prefill pool yet")
+                payload["lora"] = entry.lora
+                # only the workers that list the adapter can serve it
+                allowed = self._lora_instances(entry, entry.lora)
             try:
                 # direct routing hint (reference parity: RoutingHints
                 # backend_instance_id / RouterMode::Direct): bypass the
@@ -232,7 +269,8 @@ class ModelManager:
                 else:
                     iid = entry.router.select(
                         payload["token_ids"], session_id=session_id,
-                        override=(extra or {}).get("router_config_override"))
+                        override=(extra or {}).get("router_config_override"),
+                        allowed=allowed, score_overlap=allowed is None)
                     if iid is None:
                         raise NoInstancesError(f"no workers for {entry.name}")
                     entry.router.begin_request(iid, payload["token_ids"])

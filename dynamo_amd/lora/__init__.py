@@ -1,3 +1,3 @@
-from .manager import LoRAAdapter, LoRAManager
+from .manager import LoRAAdapter, LoRABank, LoRAManager, lora_block_salt
 
-__all__ = ["LoRAAdapter", "LoRAManager"]
+__all__ = ["LoRAAdapter", "LoRABank", "LoRAManager", "lora_block_salt"]

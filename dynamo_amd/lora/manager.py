@@ -6,13 +6,22 @@ endpoints load_lora/unload_lora/list_loras,
 components/src/dynamo/vllm/worker_factory.py:1378-1413).
 
 Design: low-rank deltas on the attention qkv/o and MLP gate_up/down
-projections (y += (x A^T) B^T * alpha/r). One adapter is ACTIVE per engine
-at a time (engine-level activation, not per-request batching): multi-
-adapter serving is achieved across workers — the router filters workers by
-the adapters they have loaded — rather than by mixing adapters inside one
-batch. Activating/deactivating invalidates captured decode graphs.
-Adapters load from a torch state-dict file or are random-initialized
-(seeded) for synthetic serving.
+projections (y += (x A^T) B^T * alpha/r). Two modes:
+
+* Adapter bank (EngineConfig.max_loras > 0): per-request adapter selection.
+  LoRABank holds up to max_loras adapters in device-resident slots; every
+  request names its adapter (or none) and the rows of one batch take their
+  own adapter through the gathered kernels of csrc/lora.hip (decode rows) or
+  two library GEMMs per prefill chunk. Loading or unloading an adapter
+  touches only its slot: captured decode graphs stay valid, since the kernels
+  read the row -> slot map from a device buffer.
+* Engine-level activation (max_loras == 0, the default): one adapter is
+  ACTIVE per engine at a time, for every request; activating/deactivating
+  invalidates captured decode graphs. Multi-adapter serving then happens
+  across workers - the router filters workers by the adapters they list.
+
+Adapters load from a torch state-dict file, an HF PEFT directory, or are
+random-initialized (seeded) for synthetic serving.
 """
 from __future__ import annotations
 
@@ -127,6 +136,147 @@ class LoRAManager:
             if hasattr(layer, "mlp"):
                 layer.mlp.lora = None
         self.active = None
+
+
+class LoRATargetBank:
+    """The adapter slots of one (layer, target) projection [N, K]:
+    A [S, R, K] and B [S, N, R] in the model dtype, ranks [S] int32 (the
+    true rank of the adapter in each slot, 0 = none) and scales [S] fp32 on
+    the device, plus host copies of ranks/scales for the prefill path."""
+
+    def __init__(self, A, B, ranks, scales, host_ranks, host_scales):
+        self.A, self.B, self.ranks, self.scales = A, B, ranks, scales
+        self.host_ranks, self.host_scales = host_ranks, host_scales
+        # what ops.lora_delta_ takes
+        self.dev = (A, B, ranks, scales)
+
+
+class LoRABank:
+    """max_loras adapter slots of rank <= max_rank for every layer's four
+    projections, allocated once; maps adapter name -> slot."""
+
+    def __init__(self, model, max_loras: int, max_rank: int):
+        if max_loras < 1:
+            raise ValueError("LoRABank needs max_loras >= 1")
+        if max_rank < 8 or max_rank % 8:
+            raise ValueError(
+                f"max_lora_rank must be a positive multiple of 8, got "
+                f"{max_rank}")
+        self.model = model
+        self.S, self.R = max_loras, max_rank
+        self.slot_of: Dict[str, int] = {}
+        layers = list(model.layers)
+        dev = dtype = None
+        for layer in layers:
+            for tgt, (w,) in _layer_targets(layer).items():
+                if not isinstance(w, torch.Tensor) or w.dim() != 2:
+                    raise ValueError(
+                        "the LoRA adapter bank needs plain 2-D projection "
+                        f"weights; {tgt} is {type(w).__name__}")
+                dev, dtype = w.device, w.dtype
+        S, R = self.S, self.R
+        self.scales = torch.zeros(S, dtype=torch.float32, device=dev)
+        self.host_scales = [0.0] * S
+        self.ranks = torch.zeros(len(layers), len(TARGETS), S,
+                                 dtype=torch.int32, device=dev)
+        self.targets: Dict[str, LoRATargetBank] = {}
+        for li, layer in enumerate(layers):
+            for tgt, (w,) in _layer_targets(layer).items():
+                N, K = w.shape
+                if N % 8 or K % 8:
+                    raise ValueError(
+                        f"layer {li} {tgt} is [{N}, {K}]: the adapter bank "
+                        "needs both to be multiples of 8")
+                tb = LoRATargetBank(
+                    torch.zeros(S, R, K, dtype=dtype, device=dev),
+                    torch.zeros(S, N, R, dtype=dtype, device=dev),
+                    self.ranks[li, TARGETS.index(tgt)], self.scales,
+                    [0] * S, self.host_scales)
+                self.targets[f"{li}.{tgt}"] = tb
+            if hasattr(layer, "attn"):
+                layer.attn.lora_bank = {
+                    t: self.targets[f"{li}.{t}"] for t in ("qkv", "o")}
+            if hasattr(layer, "mlp"):
+                layer.mlp.lora_bank = {
+                    t: self.targets[f"{li}.{t}"] for t in ("gate_up", "down")}
+
+    def list(self) -> List[str]:
+        return sorted(self.slot_of)
+
+    def slot(self, name: str) -> int:
+        return self.slot_of[name]
+
+    def load(self, name: str, path: Optional[str] = None, rank: int = 8,
+             alpha: float = 16.0, seed: int = 0) -> int:
+        """Read the adapter and copy its block-form (A, B) of every target
+        into a free slot (the slot it already has, when reloading a name)."""
+        import os
+        slot = self.slot_of.get(name)
+        if slot is None:
+            used = set(self.slot_of.values())
+            free = [s for s in range(self.S) if s not in used]
+            if not free:
+                raise ValueError(
+                    f"cannot load LoRA {name!r}: all {self.S} adapter slots "
+                    f"(max_loras) are in use by {self.list()}")
+            slot = free[0]
+        if path and os.path.isdir(path) and os.path.exists(
+                os.path.join(path, "adapter_config.json")):
+            ad = load_peft_adapter(name, path, self.model)
+        elif path:
+            ad = LoRAAdapter.load(name, path, self.model, rank, alpha)
+        else:
+            ad = LoRAAdapter.random(name, self.model, rank, alpha, seed)
+        # PEFT block forms (3r for qkv, 2r for gate/up) count against R
+        for key, (A, _B) in ad.weights.items():
+            if A.shape[0] > self.R:
+                raise ValueError(
+                    f"cannot load LoRA {name!r}: target {key} has rank "
+                    f"{A.shape[0]} (fused block form), above max_lora_rank "
+                    f"{self.R}")
+        with torch.no_grad():
+            # rank 0 first: a slot is never seen half-written with a rank
+            self.ranks[:, :, slot] = 0
+            host = torch.zeros(self.ranks.shape[:2], dtype=torch.int32)
+            for key, tb in self.targets.items():
+                # a target the adapter leaves out keeps rank 0
+                w = ad.weights.get(key)
+                r = 0 if w is None else int(w[0].shape[0])
+                if r:
+                    tb.A[slot, :r].copy_(w[0])
+                    tb.B[slot, :, :r].copy_(w[1])
+                tb.host_ranks[slot] = r
+                li, tgt = key.split(".")
+                host[int(li), TARGETS.index(tgt)] = r
+            self.ranks[:, :, slot] = host.to(self.ranks.device)
+            self.scales[slot] = ad.scale
+        self.host_scales[slot] = float(ad.scale)
+        self.slot_of[name] = slot
+        log.info("loaded LoRA %s into bank slot %d (rank %d)", name, slot,
+                 ad.rank)
+        return slot
+
+    def unload(self, name: str):
+        slot = self.slot_of.pop(name, None)
+        if slot is None:
+            return
+        with torch.no_grad():
+            self.ranks[:, :, slot] = 0
+        for tb in self.targets.values():
+            tb.host_ranks[slot] = 0
+
+
+def lora_block_salt(block_salt: int, lora: Optional[str]) -> int:
+    """The prefix-cache block salt of a request: KV computed under an adapter
+    is not the base model's, so the adapter's name is hashed in. Stable
+    across processes (TP ranks must agree); base requests keep block_salt."""
+    if not lora:
+        return block_salt
+    import hashlib
+    h = int.from_bytes(
+        hashlib.blake2b(lora.encode("utf-8"), digest_size=8).digest(),
+        "little")
+    return (block_salt ^ (h | 1)) & 0xFFFFFFFFFFFFFFFF
 
 
 # ---------------------------------------------------------------------------

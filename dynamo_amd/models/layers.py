@@ -47,6 +47,16 @@ class AttnMetadata:
     inputs_embeds: Optional[torch.Tensor] = None       # [Te, hidden]
     # V pages stored d-major (see EngineConfig.kv_v_layout)
     v_transposed: bool = False
+    # batched LoRA (EngineConfig.max_loras > 0): the adapter-bank slot of
+    # every row of the flattened batch, -1 = base model; None when no
+    # scheduled request carries an adapter
+    lora_slots: Optional[torch.Tensor] = None          # [T] int32
+    # leading decode rows that go through the gathered kernels (0 when no
+    # decode row carries an adapter)
+    lora_decode_rows: int = 0
+    # prefill chunks under an adapter: [(row0, nrows, slot)]; a chunk is
+    # contiguous and of one adapter
+    lora_prefill: Optional[list] = None
 
 
 def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -59,6 +69,26 @@ def linear_lora(x: torch.Tensor, w: torch.Tensor, lora, key: str) -> torch.Tenso
     if lora is not None and key in lora:
         A, B, scale = lora[key]
         y = y + F.linear(F.linear(x, A), B) * scale
+    return y
+
+
+def lora_bank_delta_(y: torch.Tensor, x: torch.Tensor, bank,
+                     meta: AttnMetadata) -> torch.Tensor:
+    """Add each row's own adapter delta to y = linear(x, w) in place. bank is
+    the projection's lora.LoRATargetBank. Decode rows take the gathered HIP
+    kernels, which read the row -> slot map on the device; a prefill chunk is
+    thousands of rows of one adapter and takes two library GEMMs on its
+    slot's A[:rank], B[:, :rank]."""
+    nd = meta.lora_decode_rows
+    if nd:
+        ops.lora_delta_(y[:nd], x[:nd], bank.dev, meta.lora_slots[:nd])
+    for row0, n, slot in meta.lora_prefill or ():
+        r = bank.host_ranks[slot]
+        if r:
+            xs = x[row0:row0 + n]
+            y[row0:row0 + n] += F.linear(
+                F.linear(xs, bank.A[slot, :r]),
+                bank.B[slot, :, :r]) * bank.host_scales[slot]
     return y
 
 
@@ -193,10 +223,13 @@ class Attention(torch.nn.Module):
                             if tp.size > 1 else full)
                         off += rows
         self.lora = None  # set by dynamo_amd.lora.LoRAManager
+        self.lora_bank = None  # {"qkv", "o"}, set by dynamo_amd.lora.LoRABank
 
     def forward(self, x, cos_sin, kcache, vcache, meta: AttnMetadata):
         T = x.shape[0]
         qkv = linear_lora(x, self.wqkv, self.lora, "qkv")
+        if meta.lora_slots is not None:
+            lora_bank_delta_(qkv, x, self.lora_bank["qkv"], meta)
         # fused epilogue: strided qkv read (+bias) -> rope -> q contiguous,
         # k/v scattered into the cache (one kernel vs four)
         q = ops.rope_append_qkv(qkv, self.bqkv, meta.positions,
@@ -216,7 +249,11 @@ class Attention(torch.nn.Module):
                 qh[nd:].contiguous(), kcache, vcache, meta.prefill_page_table,
                 meta.seq_q_start, meta.seq_q_len, meta.seq_ctx_len, self.scale,
                 meta.prefill_tiles, v_transposed=meta.v_transposed)
-        o = linear_lora(out.view(T, self.hq * self.hd), self.wo, self.lora, "o")
+        out = out.view(T, self.hq * self.hd)
+        o = linear_lora(out, self.wo, self.lora, "o")
+        if meta.lora_slots is not None:
+            # row-parallel: the partial deltas sum in the all-reduce below
+            lora_bank_delta_(o, out, self.lora_bank["o"], meta)
         return self.tp.all_reduce(o)
 
 
@@ -239,10 +276,16 @@ class SwiGLUMLP(torch.nn.Module):
         self.w_down = init_sharded((D, cfg.intermediate_size), device, dtype,
                                    tp, 1)
         self.lora = None  # set by dynamo_amd.lora.LoRAManager
+        self.lora_bank = None  # {"gate_up", "down"}, set by lora.LoRABank
 
-    def forward(self, x):
+    def forward(self, x, meta: Optional[AttnMetadata] = None):
+        batched = meta is not None and meta.lora_slots is not None
         gu = linear_lora(x, self.w_gate_up, self.lora, "gate_up")
+        if batched:
+            lora_bank_delta_(gu, x, self.lora_bank["gate_up"], meta)
         # silu_mul expects [., 2I] with gate then up
         act = ops.silu_mul(gu)
-        return self.tp.all_reduce(
-            linear_lora(act, self.w_down, self.lora, "down"))
+        down = linear_lora(act, self.w_down, self.lora, "down")
+        if batched:
+            lora_bank_delta_(down, act, self.lora_bank["down"], meta)
+        return self.tp.all_reduce(down)

@@ -32,7 +32,7 @@ class LlamaDecoderLayer(torch.nn.Module):
             x = ops.fused_add_rmsnorm(x, residual, self.input_norm_w, self.eps)
         x = self.attn.forward(x, cos_sin, kcache, vcache, meta)
         x = ops.fused_add_rmsnorm(x, residual, self.post_norm_w, self.eps)
-        x = self.mlp.forward(x)
+        x = self.mlp.forward(x, meta)
         return x, residual
 
 

@@ -557,3 +557,36 @@ def copy_pages(dst_cache, src_cache, pairs):
         src = pairs[:, 0].long()
         dst = pairs[:, 1].long()
         dst_cache[dst] = src_cache[src]
+
+
+# --------------------------------------------------------------------------
+# Batched LoRA (csrc/lora.hip): row i of the batch takes the adapter in bank
+# slot slots[i] (device int32, -1 = none). A bank is the tuple
+# (A_bank [S, R, K], B_bank [S, N, R], ranks [S] int32, scales [S] fp32) of
+# one (layer, target); dynamo_amd.lora.LoRABank owns them.
+def lora_shrink(t, x, A_bank, slots, ranks):
+    """t[i, r] = x[i] . A_bank[slots[i], r] for r < ranks[slots[i]], fp32."""
+    if x.is_cuda:
+        hip().lora_shrink(t, x, A_bank, slots, ranks)
+        return t
+    return torch_ref.lora_shrink(t, x, A_bank, slots, ranks)
+
+
+def lora_expand_add(y, t, B_bank, slots, ranks, scales):
+    """In place: y[i] += scales[s] * B_bank[s, :, :rank] @ t[i, :rank], one
+    rounding; rows with slots[i] < 0 stay bit-untouched."""
+    if y.is_cuda:
+        hip().lora_expand_add(y, t, B_bank, slots, ranks, scales)
+        return y
+    return torch_ref.lora_expand_add(y, t, B_bank, slots, ranks, scales)
+
+
+def lora_delta_(y, x, bank, slots):
+    """y += the per-row LoRA delta of x under `bank` (see above), in place."""
+    A_bank, B_bank, ranks, scales = bank
+    # rows and columns the kernels skip are neither written nor read
+    t = torch.empty(x.shape[0], A_bank.shape[1], dtype=torch.float32,
+                    device=x.device)
+    lora_shrink(t, x, A_bank, slots, ranks)
+    lora_expand_add(y, t, B_bank, slots, ranks, scales)
+    return y

@@ -174,3 +174,36 @@ def attention_prefill_paged(q, kcache, vcache, page_table, seq_q_start,
 
 def greedy_sample(logits: torch.Tensor) -> torch.Tensor:
     return logits.argmax(dim=-1).to(torch.int32)
+
+
+# --------------------------------------------------------------------------
+# batched LoRA: every row picks its adapter from a bank by slot
+def lora_shrink(t, x, A_bank, slots, ranks):
+    """t[i, r] = sum_k x[i, k] * A_bank[slots[i], r, k] for r < ranks[slots[i]],
+    in fp32. Rows with slots[i] < 0, and columns at r >= the rank, are not
+    written. A per-row gather: nothing of the bank outside the named slot's
+    first `rank` rows is read."""
+    sl = slots.tolist()
+    rk = ranks.tolist()
+    for i, s in enumerate(sl):
+        if s < 0 or rk[s] <= 0:
+            continue
+        r = rk[s]
+        t[i, :r] = A_bank[s, :r].float() @ x[i].float()
+    return t
+
+
+def lora_expand_add(y, t, B_bank, slots, ranks, scales):
+    """In place: y[i] = dtype(float(y[i]) + scales[s] * B_bank[s, :, :rank] @
+    t[i, :rank]) with s = slots[i]: fp32 math, one rounding to y's dtype. Rows
+    with slots[i] < 0 or rank 0 are left bit-untouched."""
+    sl = slots.tolist()
+    rk = ranks.tolist()
+    sc = scales.tolist()
+    for i, s in enumerate(sl):
+        if s < 0 or rk[s] <= 0:
+            continue
+        r = rk[s]
+        d = B_bank[s, :, :r].float() @ t[i, :r].float()
+        y[i] = (y[i].float() + sc[s] * d).to(y.dtype)
+    return y

@@ -41,6 +41,7 @@ import torch.distributed as dist
 from dynamo_amd.engine.engine import LLMEngine
 from dynamo_amd.engine.kv_cache import SequenceKV
 from dynamo_amd.engine.scheduler import SamplingParams
+from dynamo_amd.lora import lora_block_salt
 from dynamo_amd.models.layers import TPContext
 
 log = logging.getLogger("dynamo_amd.tp")
@@ -74,7 +75,8 @@ def apply_command(engine: LLMEngine, cmd: dict, tp_rank: int = 0):
         attach_remote(engine, spec, tp_rank)
     for r in cmd.get("new", []):
         req = engine.add_request(r["request_id"], r["token_ids"],
-                                 _make_sp(r["sampling"]))
+                                 _make_sp(r["sampling"]),
+                                 lora=r.get("lora"))
         if r.get("hold_kv"):
             req.hold_kv = True
         if r.get("arrival") is not None:
@@ -112,9 +114,11 @@ def attach_remote(engine: LLMEngine, spec: dict, tp_rank: int = 0):
     rank's pool, mark the prompt computed."""
     from dynamo_amd.disagg.transfer import KvPuller, rank_meta
     sp = _make_sp(spec["sampling"])
-    req = engine.add_request(spec["request_id"], spec["token_ids"], sp)
+    req = engine.add_request(spec["request_id"], spec["token_ids"], sp,
+                             lora=spec.get("lora"))
     num_tokens = int(spec["num_tokens"])
-    kv = SequenceKV(engine.alloc, engine.cfg.block_salt)
+    kv = SequenceKV(engine.alloc,
+                    lora_block_salt(engine.cfg.block_salt, req.lora))
     kv.ensure_capacity(num_tokens)
     pool = engine.runner.kv_pool
     if pool is not None and spec.get("src_meta") is not None:
@@ -153,9 +157,10 @@ class TPEngineGroup:
 
     # -- engine surface -------------------------------------------------
     def add_request(self, req_id, prompt_tokens, sampling: SamplingParams,
-                    prompt_embeds=None):
+                    prompt_embeds=None, lora=None):
         assert prompt_embeds is None, "prompt_embeds unsupported at TP>1"
-        req = self.engine.add_request(req_id, prompt_tokens, sampling)
+        req = self.engine.add_request(req_id, prompt_tokens, sampling,
+                                      lora=lora)
         self._pending_new.append(req)
         return req
 
@@ -177,6 +182,7 @@ class TPEngineGroup:
                         # (offset, tensor) pairs pickle through the gloo
                         # object broadcast; identical on every rank
                         "embed_spans": r.embed_spans,
+                        "lora": r.lora,
                         "arrival": r.arrival}
                        for r in self._pending_new],
                "aborts": self._pending_aborts, "step": step}
@@ -214,13 +220,25 @@ class TPEngineGroup:
         self._immediate({"attach": [spec]})
         return self.engine.requests.get(spec["request_id"])
 
+    def _lora_command(self, cmd: dict):
+        if self.engine.lora_bank is None:
+            return self._immediate(cmd)
+        # an adapter bank can refuse (no free slot, rank above
+        # max_lora_rank, adapter in use): rank 0 applies first, so that
+        # followers only ever see a command that succeeded
+        if self._pending_new or self._pending_aborts:
+            self._broadcast(self._pending_cmd(step=False))
+        out = apply_command(self.engine, cmd, tp_rank=0)
+        self._broadcast(cmd)
+        return out
+
     def load_lora(self, name, path=None, rank=8, alpha=16.0, seed=0):
-        self._immediate({"lora": {"op": "load", "name": name, "path": path,
-                                  "rank": rank, "alpha": alpha,
-                                  "seed": seed}})
+        self._lora_command({"lora": {"op": "load", "name": name,
+                                     "path": path, "rank": rank,
+                                     "alpha": alpha, "seed": seed}})
 
     def unload_lora(self, name):
-        self._immediate({"lora": {"op": "unload", "name": name}})
+        self._lora_command({"lora": {"op": "unload", "name": name}})
 
     def list_loras(self):
         return self.engine.list_loras()

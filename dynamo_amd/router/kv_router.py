@@ -247,8 +247,15 @@ class KvRouter:
     # -- selection ------------------------------------------------------
     def select(self, token_ids: List[int],
                session_id: Optional[str] = None,
-               override: Optional[dict] = None) -> Optional[str]:
+               override: Optional[dict] = None,
+               allowed: Optional[set] = None,
+               score_overlap: bool = True) -> Optional[str]:
         """Pick a worker instance_id for this token sequence.
+
+        allowed: restrict the choice to these instance ids (LoRA: the
+        workers that list the request's adapter); score_overlap=False costs
+        every candidate as holding no cached prefix (KV computed under an
+        adapter is salted differently from what the indexer hashes).
 
         session_id pins a session to its previous worker while that worker
         is alive (sticky sessions); busy_threshold > 0 rejects with
@@ -257,6 +264,8 @@ class KvRouter:
         kv-router/src/scheduling/config.rs) for the cost-formula weights
         and sampling temperature."""
         insts = self.client.instances()
+        if allowed is not None:
+            insts = [i for i in insts if i.instance_id in allowed]
         if not insts:
             return None
         # drop locally-inhibited instances (dead-worker watch-lag window);
@@ -280,16 +289,18 @@ class KvRouter:
             if pinned in alive:
                 self._sessions.move_to_end(session_id)
                 return pinned
-            iid = self._select_inner(insts, token_ids, override)
+            iid = self._select_inner(insts, token_ids, override,
+                                     score_overlap)
             self._sessions[session_id] = iid
             self._sessions.move_to_end(session_id)
             while len(self._sessions) > self.cfg.max_sessions:
                 self._sessions.popitem(last=False)
             return iid
-        return self._select_inner(insts, token_ids, override)
+        return self._select_inner(insts, token_ids, override, score_overlap)
 
     def _select_inner(self, insts, token_ids: List[int],
-                      override: Optional[dict] = None) -> Optional[str]:
+                      override: Optional[dict] = None,
+                      score_overlap: bool = True) -> Optional[str]:
         cfg = self.cfg
         if override:
             import dataclasses
@@ -312,9 +323,10 @@ class KvRouter:
         # kv mode
         bs = cfg.block_size
         hashes = _core.chain_hashes(token_ids, bs, cfg.block_salt)
-        matches = self.indexer.find_matches(hashes)
+        matches = self.indexer.find_matches(hashes) if score_overlap else {}
         host_matches = (self.host_indexer.find_matches(hashes)
-                        if cfg.host_overlap_weight > 0 else {})
+                        if cfg.host_overlap_weight > 0 and score_overlap
+                        else {})
         prefill_blocks = (len(token_ids) + bs - 1) // bs
         logits = []
         for inst in insts:

@@ -14,6 +14,7 @@ import os
 import signal
 import tempfile
 
+from dynamo_amd import envs
 from dynamo_amd.engine import EngineConfig, LLMEngine
 from dynamo_amd.models.registry import resolve_model_config
 from dynamo_amd.runtime import DistributedRuntime
@@ -52,6 +53,17 @@ def build_parser():
                         "microscaling FP4 (e2m1 with one e8m0 scale per 32 k, "
                         "W4A16); llama/qwen2 only; auto follows "
                         "DYNAMO_WEIGHT_DTYPE (default bf16)")
+    p.add_argument("--max-loras", type=int,
+                   default=envs.get("DYNAMO_MAX_LORAS", 0, int),
+                   help="adapter-bank slots for per-request LoRA: requests "
+                        "name a loaded adapter and share batches; 0 keeps "
+                        "one engine-activated adapter; llama/qwen2 with "
+                        "bf16 weights only")
+    p.add_argument("--max-lora-rank", type=int,
+                   default=envs.get("DYNAMO_MAX_LORA_RANK", 64, int),
+                   help="largest adapter rank a bank slot holds (multiple "
+                        "of 8; fused PEFT forms count 3r for qkv, 2r for "
+                        "gate/up)")
     p.add_argument("--kv-v-layout", default="auto",
                    choices=["auto", "never"],
                    help="V-page layout: auto = d-major on GPU when supported")
@@ -141,6 +153,8 @@ def make_engine_from_args(args, tp=None) -> LLMEngine:
         gpu_mem_fraction=args.gpu_mem_fraction,
         kv_cache_dtype=args.kv_cache_dtype,
         weight_dtype=args.weight_dtype,
+        max_loras=args.max_loras,
+        max_lora_rank=args.max_lora_rank,
         kv_v_layout=args.kv_v_layout,
         enable_prefix_caching=not args.no_prefix_caching,
         enable_hip_graphs=not args.no_hip_graphs,

@@ -363,8 +363,12 @@ class WorkerService:
                     req = await self._attach_remote_kv(req_id, tokens, sp,
                                                        pr)
                 else:
+                    # "lora": per-request adapter (bank engines); an unknown
+                    # name raises ValueError, returned to the caller
+                    kw = ({"lora": payload["lora"]}
+                          if payload.get("lora") else {})
                     req = self.engine.add_request(
-                        req_id, tokens, sp, prompt_embeds=prompt_embeds)
+                        req_id, tokens, sp, prompt_embeds=prompt_embeds, **kw)
                     if embed_spans:
                         req.embed_spans = embed_spans
                     if is_prefill_role:

@@ -28,6 +28,7 @@ hip_sources = [
         "skinny_gemm.hip",
         "sampling.hip",
         "moe.hip",
+        "lora.hip",
         "ipc.hip",
         "probe.hip",
     )
