@@ -40,6 +40,16 @@ inline int decode_chunk_tokens(int max_ctx) {
 constexpr int kChunk = DECODE_KCHUNK;  // sweep-tool default (see above)
 constexpr float kNegInf = -1e30f;
 
+// C == 1 and ctx_len == 0 (a padded row of a captured batch): no phase 2
+// runs, so phase 1 itself must leave zeros in the row's G*hd outputs of kv
+// head h - the caller's `out` is uninitialized memory and feeds the
+// o-projection. Only the early-exit branch calls this.
+__device__ __forceinline__ void zero_pad_row(short* __restrict__ out, int b,
+                                             int h, int G, int Hq, int hd) {
+  short* row = out + ((int64_t)b * Hq + (int64_t)h * G) * hd;
+  for (int i = threadIdx.x; i < G * hd; i += kBlock) row[i] = 0;
+}
+
 template <int G, int DP, int HS, int DEPTH>
 __global__ __launch_bounds__(kBlock) void paged_decode_phase1(
     float* __restrict__ partial,        // [B, Hq, C, hd] fp32
@@ -85,6 +95,8 @@ __global__ __launch_bounds__(kBlock) void paged_decode_phase1(
         float* mlp = ml + (((int64_t)b * Hq + qh) * C + c) * 2;
         mlp[0] = kNegInf; mlp[1] = 0.f;
       }
+    } else {
+      zero_pad_row(out, b, h, G, Hq, hd);
     }
     return;
   }
@@ -350,6 +362,8 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma(
         float* mlp = ml + (((int64_t)b * Hq + qh) * C + c) * 2;
         mlp[0] = kNegInf; mlp[1] = 0.f;
       }
+    } else {
+      zero_pad_row(out, b, h, G, Hq, hd);
     }
     return;
   }
@@ -707,6 +721,8 @@ __global__ __launch_bounds__(kBlock, MINW) void paged_decode_mfma_swapped(
         mlp[0] = kNegInf; mlp[1] = 0.f;
       }
       if (chunk_cnt != nullptr) fused_merge();
+    } else {
+      zero_pad_row(out, b, h, G, Hq, hd);
     }
     return;
   }
