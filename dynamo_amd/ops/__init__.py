@@ -499,7 +499,10 @@ def topk_gating(logits: torch.Tensor, k: int):
         hip().topk_gating(topw, topi, logits.float().contiguous())
         return topw, topi
     p = torch.softmax(logits.float(), dim=-1)
-    topw, topi = torch.topk(p, k, dim=-1)
+    # stable descending sort: among equal probabilities the lowest index
+    # wins, as in the kernel (torch.topk leaves tie order unspecified)
+    topw, topi = torch.sort(p, dim=-1, descending=True, stable=True)
+    topw, topi = topw[..., :k], topi[..., :k]
     return topw / topw.sum(-1, keepdim=True), topi.to(torch.int32)
 
 
