@@ -98,26 +98,26 @@ static Bufs make(int G) {
   return bf;
 }
 
-// swapped-operand MFMA variant: bench + elementwise compare vs the proven
+// swapped-operand MFMA kernels (bf16; DMAJOR: d-major V pages, NT:
+// non-temporal K/V loads): bench + elementwise compare vs the
 // paged_decode_mfma output
-template <int G, int DEFER = 1, int PRIO = 1, int KPF = 0, int VS = 80, int XK2 = 0,
-          int VT = 0, int LG2 = 0, int MINW = 1, int NTKV = 0>
+template <int G, int DMAJOR = 0, int NT = 0>
 static void run_mfma_swapped(const Bufs& bf, bool check) {
   dim3 grid(B, Hkv, bf.C);
-  // VT4/5 stage K (and V) through the per-wave v_lds region; VT1-3 skip
-  // all staging LDS
-  const int lds = (VT >= 4) ? mfma_swapped_lds_bytes(G, HD, VS)
-                : VT        ? mfma_swapped_vt_lds_bytes(G, HD)
-                            : mfma_swapped_lds_bytes(G, HD, VS);
+  const int lds = mfma_swapped_lds_bytes(G, HD);
   const int iters = 30;
+  auto* kern = [] {
+    if constexpr (DMAJOR) return &paged_decode_mfma_swapped_dmajor<0, NT>;
+    else return &paged_decode_mfma_swapped<0>;
+  }();
   if (lds > 65536)
     (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&paged_decode_mfma_swapped<DEFER, PRIO, KPF, 0, VS, XK2, VT, LG2, MINW, NTKV>),
+        reinterpret_cast<const void*>(kern),
         hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   auto launch = [&] {
-    paged_decode_mfma_swapped<DEFER, PRIO, KPF, 0, VS, XK2, VT, LG2, MINW, NTKV><<<grid, kBlock, lds>>>(
-        bf.partial, bf.ml, bf.out, bf.q, bf.kc, VT ? bf.vct : bf.vc, bf.pt, bf.ctx,
-        0.0883883f, kChunk, G, B, Hkv, bf.C, CTX / PS, 6, HD, nullptr);
+    kern<<<grid, kBlock, lds>>>(
+        bf.partial, bf.ml, bf.out, bf.q, bf.kc, DMAJOR ? bf.vct : bf.vc, bf.pt,
+        bf.ctx, 0.0883883f, kChunk, G, B, Hkv, bf.C, CTX / PS, 6, HD);
     paged_decode_phase2<<<dim3(B, G * Hkv), 128>>>(
         bf.out, bf.partial, bf.ml, bf.ctx, kChunk, G * Hkv, bf.C, HD);
   };
@@ -131,9 +131,9 @@ static void run_mfma_swapped(const Bufs& bf, bool check) {
     const int lds0 = mfma_lds_bytes(G, HD);
     if (lds0 > 65536)
       (void)hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&paged_decode_mfma<0, 0>),
+          reinterpret_cast<const void*>(&paged_decode_mfma),
           hipFuncAttributeMaxDynamicSharedMemorySize, lds0);
-    paged_decode_mfma<0, 0><<<grid, kBlock, lds0>>>(
+    paged_decode_mfma<<<grid, kBlock, lds0>>>(
         bf.partial, bf.ml, bf.out, bf.q, bf.kc, bf.vc, bf.pt, bf.ctx,
         0.0883883f, kChunk, G, B, Hkv, bf.C, CTX / PS, 6, HD);
     paged_decode_phase2<<<dim3(B, G * Hkv), 128>>>(
@@ -153,7 +153,8 @@ static void run_mfma_swapped(const Bufs& bf, bool check) {
         printf("  sw mismatch [%zu] got %f want %f\n", i,
                b2f(got[i]), b2f(ref[i]));
     }
-    printf("check G%d MFMA_SW vs MFMA: maxerr=%.4f %s\n", G, maxerr,
+    printf("check G%d MFMA_SW %s%s vs MFMA: maxerr=%.4f %s\n", G,
+           DMAJOR ? "dmajor" : "tokmajor", NT ? " nt" : "", maxerr,
            bad ? "FAIL" : "PASS");
   }
   for (int i = 0; i < 5; i++) launch();
@@ -168,22 +169,22 @@ static void run_mfma_swapped(const Bufs& bf, bool check) {
   CK(hipEventElapsedTime(&ms, e0, e1));
   double t = ms / 1000.0 / iters;
   double gb = 2.0 * B * CTX * Hkv * HD * 2 / 1e9;
-  printf("G%d MFMA_SW DF%d PR%d KP%d VS%d X%d VT%d L%d W%d NT%d %8.1f us  %7.0f GB/s\n", G,
-         DEFER, PRIO, KPF, VS, XK2, VT, LG2, MINW, NTKV, t * 1e6, gb / t);
+  printf("G%d MFMA_SW %-8s %-2s %8.1f us  %7.0f GB/s\n", G,
+         DMAJOR ? "dmajor" : "tokmajor", NT ? "nt" : "", t * 1e6, gb / t);
   fflush(stdout);
 }
 
-template <int G, int DEFER = 0, int PRIO = 0>
+template <int G>
 static void run_mfma(const Bufs& bf) {
   dim3 grid(B, Hkv, bf.C);
   const int lds = mfma_lds_bytes(G, HD);
   const int iters = 30;
   if (lds > 65536)
     (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&paged_decode_mfma<DEFER, PRIO>),
+        reinterpret_cast<const void*>(&paged_decode_mfma),
         hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   for (int i = 0; i < 5; i++)
-    paged_decode_mfma<DEFER, PRIO><<<grid, kBlock, lds>>>(
+    paged_decode_mfma<<<grid, kBlock, lds>>>(
         bf.partial, bf.ml, bf.out, bf.q, bf.kc, bf.vc, bf.pt, bf.ctx,
         0.0883883f, kChunk, G, B, Hkv, bf.C, CTX / PS, 6, HD);
   CK(hipDeviceSynchronize());
@@ -191,7 +192,7 @@ static void run_mfma(const Bufs& bf) {
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   CK(hipEventRecord(e0));
   for (int i = 0; i < iters; i++) {
-    paged_decode_mfma<DEFER, PRIO><<<grid, kBlock, lds>>>(
+    paged_decode_mfma<<<grid, kBlock, lds>>>(
         bf.partial, bf.ml, bf.out, bf.q, bf.kc, bf.vc, bf.pt, bf.ctx,
         0.0883883f, kChunk, G, B, Hkv, bf.C, CTX / PS, 6, HD);
     paged_decode_phase2<<<dim3(B, G * Hkv), 128>>>(
@@ -203,8 +204,7 @@ static void run_mfma(const Bufs& bf) {
   CK(hipEventElapsedTime(&ms, e0, e1));
   double t = ms / 1000.0 / iters;
   double gb = 2.0 * B * CTX * Hkv * HD * 2 / 1e9;
-  printf("G%d MFMA DF%d PR%d   %8.1f us  %7.0f GB/s\n", G, DEFER, PRIO,
-         t * 1e6, gb / t);
+  printf("G%d MFMA (A-operand)   %8.1f us  %7.0f GB/s\n", G, t * 1e6, gb / t);
   fflush(stdout);
 }
 
@@ -244,30 +244,14 @@ int main() {
   perm16_probe();
   {
     Bufs bf = make(8);
-    run_mfma_swapped<8, 0, 0, 0, 72, 1>(bf, true);
-    run_mfma_swapped<8, 0, 0, 0, 72, 0, 1>(bf, true);   // VT check
-    run_mfma_swapped<8, 1, 1, 0, 72, 1>(bf, false);
-    run_mfma_swapped<8, 1, 1, 0, 72, 0, 1>(bf, false);  // VT
-    run_mfma_swapped<8, 1, 0, 0, 72, 0, 1>(bf, false);  // VT no-prio
-    run_mfma_swapped<8, 0, 0, 0, 72, 0, 2>(bf, true);   // VT2 check
-    run_mfma_swapped<8, 0, 0, 0, 72, 0, 2, 1>(bf, true);  // VT2+LG2 check
-    run_mfma_swapped<8, 1, 1, 0, 72, 0, 2>(bf, false);  // VT2 pipelined
-    run_mfma_swapped<8, 0, 0, 0, 72, 0, 2, 0, 2>(bf, true);   // VT2 minw2 chk
-    run_mfma_swapped<8, 1, 1, 0, 72, 0, 2, 0, 2>(bf, false);  // VT2 minw2
-    run_mfma_swapped<8, 1, 1, 0, 72, 0, 1, 0, 3>(bf, false);  // VT1 minw3
-    run_mfma_swapped<8, 0, 0, 0, 72, 0, 3, 0, 1>(bf, true);   // VT3 64tok chk
-    run_mfma_swapped<8, 1, 1, 0, 72, 0, 3, 0, 2>(bf, false);  // VT3 minw2
-    run_mfma_swapped<8, 0, 0, 0, 72, 0, 4, 0, 1>(bf, true);   // VT4 chk
-    run_mfma_swapped<8, 1, 1, 0, 72, 0, 4, 0, 1>(bf, false);  // VT4
-    // VT4 with non-temporal K/V loads (production switch DYNAMO_DECODE_NT);
-    // K + V are 537 MB here, so the replay loop is already cache-cold
-    run_mfma_swapped<8, 0, 0, 0, 72, 0, 4, 0, 1, 1>(bf, true);   // VT4 nt chk
-    run_mfma_swapped<8, 1, 1, 0, 72, 0, 4, 0, 1, 1>(bf, false);  // VT4 nt
-    run_mfma_swapped<8, 1, 1, 0, 72, 0, 4, 0, 1>(bf, false);     // VT4 again
-    run_mfma_swapped<8, 0, 0, 0, 72, 0, 5, 0, 1>(bf, true);   // VT5 chk
-    run_mfma_swapped<8, 1, 1, 0, 72, 0, 5, 0, 1>(bf, false);  // VT5
-    run_mfma_swapped<8, 1, 1, 0, 72, 0, 5, 0, 2>(bf, false);  // VT5 minw2
-    run_mfma_swapped<8, 1, 1, 0, 72, 0, 5, 0, 3>(bf, false);  // VT5 minw3
+    // each call with `true` prints a check row, then the timing row
+    run_mfma_swapped<8>(bf, true);          // token-major V
+    run_mfma_swapped<8, 1>(bf, true);       // d-major V
+    // d-major with non-temporal K/V loads (production switch
+    // DYNAMO_DECODE_NT); K + V are 537 MB here, so the replay loop is
+    // already cache-cold
+    run_mfma_swapped<8, 1, 1>(bf, true);
+    run_mfma_swapped<8, 1>(bf, false);      // d-major again
     run<8, 16, 4, 2>(bf, "");
     run<8, 16, 4, 3>(bf, "");
     run<8, 16, 4, 4>(bf, "");
@@ -277,10 +261,7 @@ int main() {
     run<8, 8, 4, 3>(bf, "");
     run<8, 16, 1, 2>(bf, "");
     run<8, 8, 2, 2>(bf, "");
-    run_mfma<8, 0, 0>(bf);
-    run_mfma<8, 1, 0>(bf);
-    run_mfma<8, 0, 1>(bf);
-    run_mfma<8, 1, 1>(bf);
+    run_mfma<8>(bf);
   }
   {
     Bufs bf = make(4);
@@ -292,17 +273,9 @@ int main() {
     run<4, 16, 4, 2>(bf, "");
     run<4, 8, 2, 2>(bf, "");
     run<4, 8, 1, 2>(bf, "");
-    run_mfma<4, 1, 0>(bf);
-    run_mfma_swapped<4, 1, 1, 0, 88>(bf, false);
-    run_mfma_swapped<4, 0, 0, 0, 72, 0, 2>(bf, true);   // G4 VT2 check
-    run_mfma_swapped<4, 1, 1, 0, 72, 0, 2>(bf, false);  // G4 VT2
-    run_mfma_swapped<4, 1, 1, 0, 72, 0, 2, 1>(bf, false);  // G4 VT2+LG2
-    run_mfma_swapped<4, 1, 1, 0, 72, 0, 2, 0, 2>(bf, false);  // G4 VT2 minw2
-    run_mfma_swapped<4, 1, 1, 0, 72, 0, 1, 0, 3>(bf, false);  // G4 VT1 minw3
-    run_mfma_swapped<4, 1, 1, 0, 72, 0, 3, 0, 1>(bf, false);  // G4 VT3
-    run_mfma_swapped<4, 1, 1, 0, 72, 0, 3, 0, 2>(bf, false);  // G4 VT3 minw2
-    run_mfma_swapped<2, 0, 0, 0, 72, 0, 2>(bf, true);   // G2 VT2 check
-    run_mfma_swapped<2, 1, 1, 0, 72, 0, 2>(bf, false);  // G2 VT2
+    run_mfma<4>(bf);
+    run_mfma_swapped<4>(bf, false);
+    run_mfma_swapped<4, 1>(bf, true);       // G4 d-major
   }
   {
     Bufs bf = make(1);

@@ -1,15 +1,17 @@
 // Paged-attention decode kernels (torch-free; included by the extension and
 // by the standalone sweep tool benchmarks/decode_sweep.hip).
 //
-// Template space:
-//   G     : GQA group size (Hq / Hkv)
-//   DP    : lanes per token (8 or 16); dims per lane = 128/DP
-//   HS    : head-split factor (1, 2 or 4): the 4 waves form HS head-groups
-//           x (4/HS) token-groups. More head-split => smaller accumulators
-//           (occupancy) but each KV token is streamed by HS waves.
-//   DEPTH : software-pipeline depth (token groups in flight per wave).
-//           Static buffer indices only (runtime-indexed register arrays
-//           spill to scratch).
+// Four phase-1 kernels, one per (layout, arithmetic) the dispatch reaches,
+// plus the phase-2 chunk merge:
+//   paged_decode_phase1            VALU dot products, G in {1, 2, 4, 8}
+//   paged_decode_mfma              MFMA, heads on the M rows ("A-operand");
+//                                  the DYNAMO_DECODE_SWAPPED=0 fallback
+//   paged_decode_mfma_swapped      MFMA, tokens on the M rows, token-major V
+//   paged_decode_mfma_swapped_dmajor   the same with d-major ("VT4") V pages
+// The pieces they have in common (empty-chunk exit, Q staging, K/V slice
+// load, P pack, cross-wave merge + store) are the helpers below. The
+// measured history of the variants that did not ship is in
+// profiles/README.md.
 #pragma once
 #include "common.h"
 #include <cstdlib>
@@ -40,6 +42,22 @@ inline int decode_chunk_tokens(int max_ctx) {
 constexpr int kChunk = DECODE_KCHUNK;  // sweep-tool default (see above)
 constexpr float kNegInf = -1e30f;
 
+// defer-max (guide T13): while a tile's max stays within this of the
+// running max, keep the old max and skip the accumulator rescale (P is
+// bounded by e^8 - fp32 accumulation headroom).
+constexpr float kDeferMax = 8.0f;
+
+// V^T LDS row stride in bytes of the token-major swapped kernel. With 80
+// (a plain 16 B pad) rows 8 apart start at the same bank (8 * 20 banks % 32
+// == 0) and every b64 staging write is ~16-way conflicted; 72 puts them 16
+// banks apart (8 * 18 % 32 == 16), halving the conflicts with less LDS than
+// 88. The d-major kernel stages K in the same per-wave region and uses
+// 8 KB of its 9 KB.
+constexpr int kVStride = 72;
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+typedef __attribute__((ext_vector_type(2))) unsigned int uint2_t;
+
 // C == 1 and ctx_len == 0 (a padded row of a captured batch): no phase 2
 // runs, so phase 1 itself must leave zeros in the row's G*hd outputs of kv
 // head h - the caller's `out` is uninitialized memory and feeds the
@@ -50,6 +68,179 @@ __device__ __forceinline__ void zero_pad_row(short* __restrict__ out, int b,
   for (int i = threadIdx.x; i < G * hd; i += kBlock) row[i] = 0;
 }
 
+// A block whose chunk starts at or past the row's context has no tokens:
+// it publishes the empty (m, l) for phase 2, or with one chunk zeroes the
+// row itself. The caller returns right after.
+__device__ __forceinline__ void write_empty_chunk(
+    float* __restrict__ ml, short* __restrict__ out, int b, int h, int c,
+    int G, int Hq, int C, int hd) {
+  if (C > 1) {
+    for (int i = threadIdx.x; i < G; i += kBlock) {
+      const int qh = h * G + i;
+      float* mlp = ml + (((int64_t)b * Hq + qh) * C + c) * 2;
+      mlp[0] = kNegInf; mlp[1] = 0.f;
+    }
+  } else {
+    zero_pad_row(out, b, h, G, Hq, hd);
+  }
+}
+
+// The G query heads of kv head h -> LDS [G][hd] bf16, visible to the block.
+__device__ __forceinline__ void stage_q(short* __restrict__ q_lds_s,
+                                        const short* __restrict__ q, int b,
+                                        int h, int G, int Hq, int hd) {
+  for (int i = threadIdx.x; i < G * hd; i += kBlock) {
+    const int g = i / hd;
+    q_lds_s[i] = q[((int64_t)b * Hq + h * G + g) * hd + i % hd];
+  }
+  __syncthreads();
+}
+
+// Q as an MFMA 16x16x32 operand: row/col = lr (head, zero-padded beyond G),
+// k = lg*8+j (+32*kc). The same registers serve as the A operand of
+// paged_decode_mfma and as the B operand of the swapped kernels.
+__device__ __forceinline__ void load_q_frag(bf16x8_t (&q_frag)[4],
+                                            const short* q_lds_s, int G,
+                                            int hd, int lr, int lg) {
+#pragma unroll
+  for (int kc = 0; kc < 4; kc++) {
+    short8 v{};
+    if (lr < G)
+      v = *reinterpret_cast<const short8*>(q_lds_s + lr * hd + kc * 32 + lg * 8);
+    q_frag[kc] = *reinterpret_cast<bf16x8_t*>(&v);
+  }
+}
+
+// One 8-element K/V slice as a bf16x8-compatible short8.
+//   FP8: the paged cache stores OCP e4m3 bytes at the same ELEMENT offsets
+//        (halves decode HBM traffic); converted to bf16 here via packed
+//        v_cvt (decode is HBM-bound, the converts hide under MFMA/memory).
+//   NT:  non-temporal cache policy (global_load ... nt). K/V bytes are read
+//        once per step by one wave, so they need not displace Q, the page
+//        table or the partials in the caches. Addresses and arithmetic are
+//        unchanged: outputs are bit-identical.
+template <int FP8, int NT>
+__device__ __forceinline__ short8 ld8(const short* base, int64_t elem_off) {
+  if constexpr (FP8) {
+    const unsigned char* b =
+        reinterpret_cast<const unsigned char*>(base) + elem_off;
+    uchar8 raw;
+    if constexpr (NT)
+      raw = __builtin_nontemporal_load(reinterpret_cast<const uchar8*>(b));
+    else
+      raw = *reinterpret_cast<const uchar8*>(b);
+    bf16x8 cv = fp8x8_to_bf16x8(raw);
+    return *reinterpret_cast<short8*>(&cv);
+  } else {
+    if constexpr (NT)
+      return __builtin_nontemporal_load(
+          reinterpret_cast<const short8*>(base + elem_off));
+    else
+      return *reinterpret_cast<const short8*>(base + elem_off);
+  }
+}
+
+// Swapped kernels, softmax state update for one tile: fold the lane's tile
+// max over the 4 token groups (lg) and apply the defer-max rescale. After
+// the fold mt is uniform over the lanes of head lr, so the branch needs no
+// vote; the O rescale is one scalar multiply per accumulator.
+__device__ __forceinline__ void swapped_update_max(float mt, float& m_run,
+                                                   float& l_run,
+                                                   f32x4 (&acc)[8]) {
+  mt = fmaxf(mt, __shfl_xor(mt, 16, WAVE_SIZE));
+  mt = fmaxf(mt, __shfl_xor(mt, 32, WAVE_SIZE));
+  if (mt > m_run + kDeferMax) {
+    const float corr = (m_run <= kNegInf * 0.5f) ? 0.f : __expf(m_run - mt);
+    l_run *= corr;
+#pragma unroll
+    for (int d = 0; d < 8; d++) acc[d] *= corr;
+    m_run = mt;
+  }
+}
+
+// Swapped kernels, P^T -> PV B-fragment in registers: two 16-token S^T
+// tiles (pa = tokens lg*4+r, pb = the same +16; 4 C/D rows each) become the
+// lane's 8 consecutive tokens 8*lg+j of one 32-token B-fragment with
+// 4 v_cvt_pk_bf16_f32 + 4 permlane swaps. Swap semantics (probed, see
+// decode_sweep's perm16_probe): permlane32_swap(v0, v1) -> x = {lo: v0(l),
+// hi: v1(l-32)}, y = {lo: v0(l+32), hi: v1(l)}; permlane16_swap the same
+// within each 32-half. So
+//   after s1 = permlane32_swap(A0, B0):
+//     x1@lg{0,1} = A0(lg),   x1@lg{2,3} = B0(lg-2)
+//     y1@lg{0,1} = A0(lg+2), y1@lg{2,3} = B0(lg)
+//   after s2 = permlane16_swap(x1, y1):
+//     x2@lg = (correct tile)(2*(lg&1)),  y2@lg = (correct tile)(2*(lg&1)+1)
+// which is exactly B-frag words {tok 8lg+0..1} and {tok 8lg+4..5}; the
+// (A1, B1) pair gives {8lg+2..3} and {8lg+6..7}.
+__device__ __forceinline__ bf16x8_t pack_p_frag(const float* pa,
+                                                const float* pb) {
+  auto cvtpk = [](float a, float bb) {
+    unsigned int r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(bb));
+    return r;
+  };
+  const unsigned int A0 = cvtpk(pa[0], pa[1]), A1 = cvtpk(pa[2], pa[3]);
+  const unsigned int B0 = cvtpk(pb[0], pb[1]), B1 = cvtpk(pb[2], pb[3]);
+  uint2_t s1 = __builtin_amdgcn_permlane32_swap(A0, B0, false, false);
+  uint2_t s2 = __builtin_amdgcn_permlane32_swap(A1, B1, false, false);
+  uint2_t f02 = __builtin_amdgcn_permlane16_swap(s1.x, s1.y, false, false);
+  uint2_t f13 = __builtin_amdgcn_permlane16_swap(s2.x, s2.y, false, false);
+  unsigned int w[4] = {f02.x, f13.x, f02.y, f13.y};
+  return *reinterpret_cast<bf16x8_t*>(w);
+}
+
+// Cross-wave merge + store. Each of the TG token groups (waves splitting
+// the chunk's tokens) has written its (acc[hd], m, l) per head into
+// merge[TG][G][hd+2]; combine them and write `out` (C == 1) or this
+// chunk's partial and (m, l) for phase 2.
+template <int TG>
+__device__ __forceinline__ void merge_groups_store(
+    const float* merge, float* __restrict__ partial, float* __restrict__ ml,
+    short* __restrict__ out, int b, int h, int c, int G, int Hq, int C,
+    int hd) {
+  __syncthreads();
+  for (int i = threadIdx.x; i < G * hd; i += kBlock) {
+    const int g = i / hd;
+    const int d = i % hd;
+    float mw[TG], lw[TG];
+    float mstar = kNegInf;
+#pragma unroll
+    for (int w = 0; w < TG; w++) {
+      mw[w] = merge[w * G * (hd + 2) + g * (hd + 2) + hd];
+      lw[w] = merge[w * G * (hd + 2) + g * (hd + 2) + hd + 1];
+      mstar = fmaxf(mstar, mw[w]);
+    }
+    float lsum = 0.f, asum = 0.f;
+#pragma unroll
+    for (int w = 0; w < TG; w++) {
+      const float corr = (lw[w] > 0.f) ? __expf(mw[w] - mstar) : 0.f;
+      lsum += lw[w] * corr;
+      asum += merge[w * G * (hd + 2) + g * (hd + 2) + d] * corr;
+    }
+    const int qh = h * G + g;
+    if (C == 1) {
+      out[((int64_t)b * Hq + qh) * hd + d] =
+          f32_to_bf16(lsum > 0.f ? asum / lsum : 0.f);
+    } else {
+      partial[(((int64_t)b * Hq + qh) * C + c) * hd + d] = asum;
+      if (d == 0) {
+        float* mlp = ml + (((int64_t)b * Hq + qh) * C + c) * 2;
+        mlp[0] = mstar; mlp[1] = lsum;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// VALU kernel. Template space:
+//   G     : GQA group size (Hq / Hkv)
+//   DP    : lanes per token (8 or 16); dims per lane = 128/DP
+//   HS    : head-split factor (1, 2 or 4): the 4 waves form HS head-groups
+//           x (4/HS) token-groups. More head-split => smaller accumulators
+//           (occupancy) but each KV token is streamed by HS waves.
+//   DEPTH : software-pipeline depth (token groups in flight per wave).
+//           Static buffer indices only (runtime-indexed register arrays
+//           spill to scratch).
 template <int G, int DP, int HS, int DEPTH>
 __global__ __launch_bounds__(kBlock) void paged_decode_phase1(
     float* __restrict__ partial,        // [B, Hq, C, hd] fp32
@@ -89,23 +280,10 @@ __global__ __launch_bounds__(kBlock) void paged_decode_phase1(
   short* q_lds_s = reinterpret_cast<short*>(lds + (TG > 1 ? TG * G * (hd + 2) : 0));
 
   if (chunk_start >= ctx) {
-    if (C > 1) {
-      for (int i = threadIdx.x; i < G; i += kBlock) {
-        const int qh = h * G + i;
-        float* mlp = ml + (((int64_t)b * Hq + qh) * C + c) * 2;
-        mlp[0] = kNegInf; mlp[1] = 0.f;
-      }
-    } else {
-      zero_pad_row(out, b, h, G, Hq, hd);
-    }
+    write_empty_chunk(ml, out, b, h, c, G, Hq, C, hd);
     return;
   }
-
-  for (int i = threadIdx.x; i < G * hd; i += kBlock) {
-    const int g = i / hd;
-    q_lds_s[i] = q[((int64_t)b * Hq + h * G + g) * hd + i % hd];
-  }
-  __syncthreads();
+  stage_q(q_lds_s, q, b, h, G, Hq, hd);
 
   // q kept packed bf16; QK dot uses v_dot2_f32_bf16 (2 MACs/inst, no
   // converts — 3x fewer VALU ops than cvt+fma per element)
@@ -268,69 +446,37 @@ __global__ __launch_bounds__(kBlock) void paged_decode_phase1(
       if (dp == 0) { my[gq * (hd + 2) + hd] = m[g]; my[gq * (hd + 2) + hd + 1] = l[g]; }
     }
   }
-  __syncthreads();
-
-  for (int i = threadIdx.x; i < G * hd; i += kBlock) {
-    const int g = i / hd;
-    const int d = i % hd;
-    float mw[TG], lw[TG];
-    float mstar = kNegInf;
-#pragma unroll
-    for (int w = 0; w < TG; w++) {
-      mw[w] = merge[w * G * (hd + 2) + g * (hd + 2) + hd];
-      lw[w] = merge[w * G * (hd + 2) + g * (hd + 2) + hd + 1];
-      mstar = fmaxf(mstar, mw[w]);
-    }
-    float lsum = 0.f, asum = 0.f;
-#pragma unroll
-    for (int w = 0; w < TG; w++) {
-      const float corr = (lw[w] > 0.f) ? __expf(mw[w] - mstar) : 0.f;
-      lsum += lw[w] * corr;
-      asum += merge[w * G * (hd + 2) + g * (hd + 2) + d] * corr;
-    }
-    const int qh = h * G + g;
-    if (C == 1) {
-      out[((int64_t)b * Hq + qh) * hd + d] =
-          f32_to_bf16(lsum > 0.f ? asum / lsum : 0.f);
-    } else {
-      partial[(((int64_t)b * Hq + qh) * C + c) * hd + d] = asum;
-      if (d == 0) {
-        float* mlp = ml + (((int64_t)b * Hq + qh) * C + c) * 2;
-        mlp[0] = mstar; mlp[1] = lsum;
-      }
-    }
-  }
+  merge_groups_store<TG>(merge, partial, ml, out, b, h, c, G, Hq, C, hd);
 }
 
 // ---------------------------------------------------------------------------
-// MFMA decode variant: the GQA group rides the MFMA M dimension, so the
-// per-head VALU cost of the dot/accumulate path disappears (measured: the
-// VALU kernel scales 4978 -> 2467 GB/s from G=1 to G=8; this variant keeps
-// the G=1 rate for G=8).
+// MFMA decode, A-operand variant: the GQA group rides the MFMA M dimension,
+// so the per-head VALU cost of the dot/accumulate path disappears (measured:
+// the VALU kernel scales 4978 -> 2467 GB/s from G=1 to G=8; this variant
+// keeps the G=1 rate for G=8).
 //   S   = Q[G<=16 pad, 128] x K^T[128, 16 toks]   (K B-frags read DIRECTLY
 //         from the paged cache — no LDS staging for K)
 //   P   row-major via a small per-wave LDS tile (C/D -> A-frag re-layout)
-//   PV  = P[16, 32 toks] x V[32 toks, 128]; V staged per-wave in an LDS
-//         layout matching ds_read_b64_tr_b16's native transpose pattern
-//         (slab-permuted 4x16 blocks), so B-frags cost 2 tr-reads each.
+//   PV  = P[16, 32 toks] x V[32 toks, 128]; V staged per-wave in LDS
+//         TRANSPOSED ([128 dims][32 toks], 80-byte rows), so each B-frag is
+//         one plain b128 row read. (ds_read_b64_tr_b16 cannot do the
+//         transpose here - see the note in the body.)
 // Softmax runs on the C/D layout: row = head (4 per lane), col = token
-// (16 lanes), reductions are 4 shfl per row per 16 tokens.
+// (16 lanes), reductions are 4 shfl per row per 16 tokens, with the
+// defer-max skip (kDeferMax) and s_setprio(1) around the MFMA clusters
+// (guide T5).
 // Requires page_size % 32 == 0 and hd == 128. G (<= 16) is RUNTIME — the
 // group only appears in bounds/guards, never in register shapes, so one
 // kernel serves every GQA group (e.g. qwen2's G=7).
-//   DEFER: defer-max rescale skip (guide T13): while the tile max stays
-//          within 8 of the running max, keep m_old and skip the
-//          8xf32x4 acc rescale (P bounded by e^8 — fp32 accum headroom).
-//   PRIO:  s_setprio(1) around the MFMA clusters (guide T5).
-template <int DEFER = 0, int PRIO = 0>
-__global__ __launch_bounds__(kBlock) void paged_decode_mfma(
+// (`inline`, like paged_decode_phase2: a non-template kernel defined in a
+// header. Every translation unit that includes the header emits it.)
+__global__ __launch_bounds__(kBlock) inline void paged_decode_mfma(
     float* __restrict__ partial, float* __restrict__ ml,
     short* __restrict__ out, const short* __restrict__ q,
     const short* __restrict__ kcache, const short* __restrict__ vcache,
     const int32_t* __restrict__ page_table, const int32_t* __restrict__ ctx_lens,
     float scale, int chunk, int G, int B, int Hkv, int C, int max_pages,
     int log2_ps, int hd) {
-  typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
   const int kSlab = chunk / 4;        // tokens per wave
   const int b = blockIdx.x;
   const int h = blockIdx.y;
@@ -356,33 +502,12 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma(
   short* p_lds = q_lds_s + G * hd + 4 * 5120 + wid * 512;  // per-wave 1KB
 
   if (chunk_start >= ctx) {
-    if (C > 1) {
-      for (int i = threadIdx.x; i < G; i += kBlock) {
-        const int qh = h * G + i;
-        float* mlp = ml + (((int64_t)b * Hq + qh) * C + c) * 2;
-        mlp[0] = kNegInf; mlp[1] = 0.f;
-      }
-    } else {
-      zero_pad_row(out, b, h, G, Hq, hd);
-    }
+    write_empty_chunk(ml, out, b, h, c, G, Hq, C, hd);
     return;
   }
-
-  for (int i = threadIdx.x; i < G * hd; i += kBlock) {
-    const int g = i / hd;
-    q_lds_s[i] = q[((int64_t)b * Hq + h * G + g) * hd + i % hd];
-  }
-  __syncthreads();
-
-  // A-frags: row = lr (head, zero-padded beyond G), k = lg*8+j (+32*kc)
+  stage_q(q_lds_s, q, b, h, G, Hq, hd);
   bf16x8_t q_frag[4];
-#pragma unroll
-  for (int kc = 0; kc < 4; kc++) {
-    short8 v{};
-    if (lr < G)
-      v = *reinterpret_cast<const short8*>(q_lds_s + lr * hd + kc * 32 + lg * 8);
-    q_frag[kc] = *reinterpret_cast<bf16x8_t*>(&v);
-  }
+  load_q_frag(q_frag, q_lds_s, G, hd, lr, lg);
 
   float m[4], l[4];
   f32x4 acc[8];
@@ -400,8 +525,8 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma(
   // four 64-bit rows at the addresses of subgroup-leader lanes {0,4,8,12}
   // and hands every lane column (lane&3) of that 4x4 tile. Only 4 distinct
   // columns reach a 16-lane group, so it cannot feed a 16-column MFMA
-  // B-fragment; the PV path therefore reads the transposed V fragments as
-  // swizzled scalar LDS loads instead.
+  // B-fragment; the PV path therefore writes V transposed (packed b64
+  // stores) and reads the B-fragments as plain b128 rows.
 
   // Uniform tile count across ALL waves (inactive waves still hit the
   // barriers — __syncthreads inside a loop with per-wave iteration counts
@@ -419,7 +544,7 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma(
       const short* krA = kcache + pbase + (int64_t)(tA & (ps - 1)) * hd;
       const short* krB = kcache + pbase + (int64_t)(tB & (ps - 1)) * hd;
       const bool vA = tA < slab_end, vB = tB < slab_end;
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int kc = 0; kc < 4; kc++) {
         short8 ka = vA ? *reinterpret_cast<const short8*>(krA + kc * 32 + lg * 8)
@@ -436,14 +561,13 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma(
               q_frag[kc], *reinterpret_cast<bf16x8_t*>(&kb2), sB, 0, 0, 0);
         }
       }
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
     }
     // ---- stage V^T tile (128 dims x 32 toks, 80B row stride) ----
     // unit = (8-dim chunk, 4-token group): 4 b128 global loads, then 8
     // b64 packed transpose writes (4 toks each) — 16 b64 writes/lane/tile
     // and NO scalar LDS traffic on either side of the transpose.
     if (active) {
-      typedef __attribute__((ext_vector_type(4))) short short4v;
 #pragma unroll
       for (int u = 0; u < 2; u++) {
         const int unit = lane + u * 64;  // 128 units = 16 d8 x 8 tokgroups
@@ -478,8 +602,7 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma(
       float mt = row16_reduce_max(fmaxf(a, bb));
       // defer-max: mt is row-uniform after the reduce, so the skip
       // condition is uniform across the row's 16 lanes (no vote needed)
-      const float thr = DEFER ? 8.0f : 0.0f;
-      if (mt > m[r] + thr) {
+      if (mt > m[r] + kDeferMax) {
         const float corr = (m[r] <= kNegInf * 0.5f) ? 0.f : __expf(m[r] - mt);
         l[r] *= corr;
 #pragma unroll
@@ -516,7 +639,7 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma(
           (char*)p_lds + row * 64 + ((lg * 16) ^ x));
     }
     bf16x8_t pa = *reinterpret_cast<bf16x8_t*>(&pa_s);
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int db = 0; db < 8; db++) {
       // B-frag: lane holds V[tok = 8*lg + j][dim = db*16 + lr], j = 0..7 —
@@ -527,12 +650,12 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma(
       acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vbf, acc[db],
                                                         0, 0, 0);
     }
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     }  // active
     __builtin_amdgcn_wave_barrier();
   }
 
-  // ---- cross-wave merge (same scheme as the VALU kernel) ----
+  // ---- cross-wave merge: acc[db][r] is O[head lg*4+r][dim db*16+lr] ----
   __syncthreads();
   float* my = merge + wid * G * (hd + 2);
 #pragma unroll
@@ -548,38 +671,7 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma(
       }
     }
   }
-  __syncthreads();
-
-  for (int i = threadIdx.x; i < G * hd; i += kBlock) {
-    const int g = i / hd;
-    const int d = i % hd;
-    float mw[4], lw[4];
-    float mstar = kNegInf;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-      mw[w] = merge[w * G * (hd + 2) + g * (hd + 2) + hd];
-      lw[w] = merge[w * G * (hd + 2) + g * (hd + 2) + hd + 1];
-      mstar = fmaxf(mstar, mw[w]);
-    }
-    float lsum = 0.f, asum = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-      const float corr = (lw[w] > 0.f) ? __expf(mw[w] - mstar) : 0.f;
-      lsum += lw[w] * corr;
-      asum += merge[w * G * (hd + 2) + g * (hd + 2) + d] * corr;
-    }
-    const int qh = h * G + g;
-    if (C == 1) {
-      out[((int64_t)b * Hq + qh) * hd + d] =
-          f32_to_bf16(lsum > 0.f ? asum / lsum : 0.f);
-    } else {
-      partial[(((int64_t)b * Hq + qh) * C + c) * hd + d] = asum;
-      if (d == 0) {
-        float* mlp = ml + (((int64_t)b * Hq + qh) * C + c) * 2;
-        mlp[0] = mstar; mlp[1] = lsum;
-      }
-    }
-  }
+  merge_groups_store<4>(merge, partial, ml, out, b, h, c, G, Hq, C, hd);
 }
 
 inline int mfma_lds_bytes(int G, int hd) {
@@ -590,78 +682,54 @@ inline int mfma_lds_bytes(int G, int hd) {
 // SWAPPED-operand MFMA decode: S^T = mfma(K, Q) puts TOKENS on the MFMA M
 // rows and HEADS on the columns, so each lane's softmax state is ONE
 // head's (m, l) scalar and — crucially — the P -> PV-B-fragment
-// re-layout becomes 4 v_cvt_pk_bf16_f32 + 4 permlane swaps IN REGISTERS
-// (verified swap semantics: permlane32_swap(v0,v1) -> x = {lo: v0(l),
-// hi: v1(l-32)}, y = {lo: v0(l+32), hi: v1(l)}; permlane16_swap the same
-// within each 32-half). This deletes the per-tile P LDS roundtrip and its
-// wave-level waitcnt fence of paged_decode_mfma, and the O rescale is one
-// scalar multiply (no per-row alpha shuffles). PV computes
-// O^T = mfma(V^T, P^T); K loads, V^T staging and the cross-wave merge
-// keep the same shapes. Derivation of the swap network:
-//   after s1 = permlane32_swap(A0, B0):
-//     x1@lg{0,1} = A0(lg),   x1@lg{2,3} = B0(lg-2)
-//     y1@lg{0,1} = A0(lg+2), y1@lg{2,3} = B0(lg)
-//   after s2 = permlane16_swap(x1, y1):
-//     x2@lg = (correct tile)(2*(lg&1)),  y2@lg = (correct tile)(2*(lg&1)+1)
-// which is exactly B-frag words {tok 8lg+0..1} and {tok 8lg+4..5}; the
-// (A1, B1) pair gives {8lg+2..3} and {8lg+6..7}.
-// KPF: cross-tile register prefetch (T14 async-stage) — MEASURED 2.5x
-// WORSE (1.4 vs 3.5 TB/s, k2048 sweep): the `kfr[cur]` runtime-indexed
-// register double-buffer goes to scratch (guide rule #20), exactly the
-// round-1 K-prefetch regression repeated. Kept compiled for the sweep's
-// record; production uses KPF=0.
-// FP8: the paged cache stores OCP e4m3 bytes (halves decode HBM traffic);
-// fragments convert to bf16 in-kernel via packed v_cvt (guide: decode is
-// HBM-bound, VALU converts are free under the MFMA/mem overlap).
-// VS: V^T LDS row stride in BYTES. 80 (the original) makes the write
-// pattern collapse: rows step 8 apart start at the same bank
-// (8*20 banks % 32 == 0), so each b64 staging write is ~16-way
-// conflicted (PMC: 2.3e9 SQ_LDS_BANK_CONFLICT). An 88B stride gives
-// rows-step-8 a 16-bank offset (8*22 % 32 == 16), halving write
-// conflicts; 72 ditto with less LDS.
-// XK2: XOR the token-group slot with bit d>>4 (<<5 bytes): per write
-// instruction the (d step 8) row-groups collapse to 2 bank starts; the
-// extra key doubles the distinct byte-slots (8 -> 16, i.e. ~4-way
-// writes). Reads shift whole 16B pairs (key constant per row), so the
-// b128 PV reads stay aligned.
-// VT: the V cache pages are stored TRANSPOSED (d-major: elem offset
-// d * page_size + token_in_page instead of token_in_page * hd + d). The
-// PV A-fragment (V^T[dim][8 consecutive tokens]) is then ONE contiguous
-// b128 global load per da - the whole load_v/store_v/ds_read staging
-// pipeline (16 ds_writes + ~64 VALU packs + 8 ds_reads per tile, the
-// kernel's VALU bottleneck: PMC VALU:MFMA was 28:1) disappears. The
-// write side pays ~32x DRAM amplification ONLY for single-token decode
-// appends (~10 MB/step vs 22 GB/step of V reads); prefill appends cover
-// whole 64B lines in L2 before eviction.
-// LG2: softmax in the log2 domain + interior-tile mask elision. The
-// per-element chain mul(scale)+sub+mul(log2e)+exp collapses to
-// fma(s, scale*log2e, -m') + v_exp (saves 16 VALU/tile), and interior
-// tiles (t0+32 <= slab_end) skip the 8 cmp+sel masks. m is converted
-// back to the natural-log domain at the merge so phase2 is unchanged.
-// MINW: minimum waves/SIMD the register allocator must honor (the VT2
-// double-buffer costs 285 VGPR+AGPR = 1 wave/SIMD; forcing 2 trades
-// registers for occupancy - decide by measurement, watch ScratchSize)
-// NTKV: every K and V load (ld8) uses the non-temporal cache policy
-// (global_load ... nt). K/V bytes are read once per step by one wave, so
-// they need not displace Q, the page table or the partials in the caches.
-// Arithmetic and load addresses are unchanged: outputs are bit-identical.
-template <int DEFER = 1, int PRIO = 1, int KPF = 0, int FP8 = 0,
-          int VS = 80, int XK2 = 0, int VT = 0, int LG2 = 0, int MINW = 1,
-          int NTKV = 0>
-__global__ __launch_bounds__(kBlock, MINW) void paged_decode_mfma_swapped(
+// re-layout happens IN REGISTERS (pack_p_frag). This deletes the per-tile
+// P LDS roundtrip and its wave-level waitcnt fence of paged_decode_mfma,
+// and the O rescale is one scalar multiply (no per-row alpha shuffles).
+// PV computes O^T = mfma(V^T, P^T). Same requirements as
+// paged_decode_mfma. There is one kernel per V page layout; the two differ
+// in how V^T[dim][8 consecutive tokens], the PV A-fragment, reaches
+// registers. Both take the same LDS (mfma_swapped_lds_bytes): merge scratch
+// 4*G*(hd+2) fp32 + q G*hd bf16 + 4 per-wave regions of hd*kVStride bytes.
+
+// Cross-wave merge of the swapped kernels: acc[da][r] is
+// O^T[dim da*16+lg*4+r][head lr]; m_run/l_run are replicated over lg.
+__device__ __forceinline__ void swapped_merge_store(
+    float* merge, const f32x4 (&acc)[8], float m_run, float l_run,
+    float* __restrict__ partial, float* __restrict__ ml,
+    short* __restrict__ out, int b, int h, int c, int G, int Hq, int C, int hd,
+    int wid, int lr, int lg) {
+  __syncthreads();
+  float* my = merge + wid * G * (hd + 2);
+  if (lr < G) {
+#pragma unroll
+    for (int da = 0; da < 8; da++)
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+        my[lr * (hd + 2) + da * 16 + lg * 4 + r] = acc[da][r];
+    if (lg == 0) {
+      my[lr * (hd + 2) + hd] = m_run;
+      my[lr * (hd + 2) + hd + 1] = l_run;
+    }
+  }
+  merge_groups_store<4>(merge, partial, ml, out, b, h, c, G, Hq, C, hd);
+}
+
+// Token-major V pages ([P, Hkv, ps, hd], like K): 32-token tiles. Each
+// wave transposes its V tile through its own LDS region: 8 b128 global
+// loads, 16 packed b64 writes (4 tokens of one dim each), and one b128
+// read per PV A-fragment. Rows are kVStride bytes apart and the 8-byte
+// token-group slot is XORed with bit (d >> 4) << 5, which doubles the
+// distinct byte slots one write instruction touches (~4-way instead of
+// ~8-way writes); the key is constant per row, so reads shift whole 16 B
+// pairs and stay aligned. K fragments are read directly from the cache.
+template <int FP8>
+__global__ __launch_bounds__(kBlock) void paged_decode_mfma_swapped(
     float* __restrict__ partial, float* __restrict__ ml,
     short* __restrict__ out, const short* __restrict__ q,
     const short* __restrict__ kcache, const short* __restrict__ vcache,
     const int32_t* __restrict__ page_table, const int32_t* __restrict__ ctx_lens,
     float scale, int chunk, int G, int B, int Hkv, int C, int max_pages,
-    int log2_ps, int hd, int32_t* __restrict__ chunk_cnt) {
-  // chunk_cnt (optional, [B*Hkv] zero-initialized): fused chunk merge.
-  // When non-null and C > 1, every block of a (b, h) column counts down
-  // via atomicAdd after publishing its partial/ml; the LAST block inlines
-  // the phase2 merge and resets the counter - one kernel launch instead
-  // of two per decode layer (~0.45 ms/step on the 80-layer flagship).
-  typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-  typedef __attribute__((ext_vector_type(2))) unsigned int uint2_t;
+    int log2_ps, int hd) {
   const int kSlab = chunk / 4;
   const int b = blockIdx.x;
   const int h = blockIdx.y;
@@ -678,70 +746,15 @@ __global__ __launch_bounds__(kBlock, MINW) void paged_decode_mfma_swapped(
   extern __shared__ float lds[];
   float* merge = lds;                                   // 4*G*(hd+2)
   short* q_lds_s = reinterpret_cast<short*>(merge + 4 * G * (hd + 2));
-  short* v_lds = q_lds_s + G * hd + wid * (hd * VS / 2);  // per-wave
-
-  auto fused_merge = [&]() {
-    // countdown; the last-arriving block of this (b, h) column merges
-    __threadfence();
-    __shared__ int lastflag;
-    if (threadIdx.x == 0) {
-      const int prev = atomicAdd(&chunk_cnt[b * Hkv + h], 1);
-      lastflag = (prev == (int)gridDim.z - 1) ? 1 : 0;
-    }
-    __syncthreads();
-    if (!lastflag) return;
-    __threadfence();  // acquire the other blocks' partial/ml stores
-    if (threadIdx.x == 0) chunk_cnt[b * Hkv + h] = 0;  // next-launch reset
-    const int nc = min(C, (ctx + chunk - 1) / chunk);
-    for (int i = threadIdx.x; i < G * hd; i += kBlock) {
-      const int g = i / hd;
-      const int d = i % hd;
-      const int qh = h * G + g;
-      const float* mlp = ml + (((int64_t)b * Hq + qh) * C) * 2;
-      float mstar = kNegInf;
-      for (int cc = 0; cc < nc; cc++) mstar = fmaxf(mstar, mlp[2 * cc]);
-      float asum = 0.f, lsum2 = 0.f;
-      for (int cc = 0; cc < nc; cc++) {
-        const float lc = mlp[2 * cc + 1];
-        if (lc <= 0.f) continue;
-        const float corr = __expf(mlp[2 * cc] - mstar);
-        asum += partial[(((int64_t)b * Hq + qh) * C + cc) * hd + d] * corr;
-        lsum2 += lc * corr;
-      }
-      out[((int64_t)b * Hq + qh) * hd + d] =
-          f32_to_bf16(lsum2 > 0.f ? asum / lsum2 : 0.f);
-    }
-  };
+  short* v_lds = q_lds_s + G * hd + wid * (hd * kVStride / 2);  // per-wave
 
   if (chunk_start >= ctx) {
-    if (C > 1) {
-      for (int i = threadIdx.x; i < G; i += kBlock) {
-        const int qh = h * G + i;
-        float* mlp = ml + (((int64_t)b * Hq + qh) * C + c) * 2;
-        mlp[0] = kNegInf; mlp[1] = 0.f;
-      }
-      if (chunk_cnt != nullptr) fused_merge();
-    } else {
-      zero_pad_row(out, b, h, G, Hq, hd);
-    }
+    write_empty_chunk(ml, out, b, h, c, G, Hq, C, hd);
     return;
   }
-
-  for (int i = threadIdx.x; i < G * hd; i += kBlock) {
-    const int g = i / hd;
-    q_lds_s[i] = q[((int64_t)b * Hq + h * G + g) * hd + i % hd];
-  }
-  __syncthreads();
-
-  // Q as the QK B-operand: same fragment registers as the A-frag variant
+  stage_q(q_lds_s, q, b, h, G, Hq, hd);
   bf16x8_t q_frag[4];
-#pragma unroll
-  for (int kc = 0; kc < 4; kc++) {
-    short8 v{};
-    if (lr < G)
-      v = *reinterpret_cast<const short8*>(q_lds_s + lr * hd + kc * 32 + lg * 8);
-    q_frag[kc] = *reinterpret_cast<bf16x8_t*>(&v);
-  }
+  load_q_frag(q_frag, q_lds_s, G, hd, lr, lg);
 
   // per-lane softmax state for head `lr` (replicated across the 4 lg
   // groups); acc[da][r] = O^T[dim da*16 + lg*4 + r][head lr]
@@ -754,169 +767,81 @@ __global__ __launch_bounds__(kBlock, MINW) void paged_decode_mfma_swapped(
   const int slab_end = min(slab_start + kSlab, ctx);
   const int32_t* pt = page_table + (int64_t)b * max_pages;
 
-  // prefetchable loads (KPF): K fragments (8x short8) + V staging rows
-  // (8x short8) per tile, double-buffered across iterations
-  typedef __attribute__((ext_vector_type(4))) short short4v;
-  auto ld8 = [&](const short* base, int64_t elem_off) -> short8 {
-    // one 8-element K/V slice as a bf16x8-compatible short8; FP8 caches
-    // hold bytes at the same ELEMENT offsets
-    if constexpr (FP8) {
-      const unsigned char* b =
-          reinterpret_cast<const unsigned char*>(base) + elem_off;
-      uchar8 raw;
-      if constexpr (NTKV)
-        raw = __builtin_nontemporal_load(reinterpret_cast<const uchar8*>(b));
-      else
-        raw = *reinterpret_cast<const uchar8*>(b);
-      bf16x8 cv = fp8x8_to_bf16x8(raw);
-      return *reinterpret_cast<short8*>(&cv);
-    } else {
-      if constexpr (NTKV)
-        return __builtin_nontemporal_load(
-            reinterpret_cast<const short8*>(base + elem_off));
-      else
-        return *reinterpret_cast<const short8*>(base + elem_off);
-    }
-  };
-  auto load_k = [&](int t0_, short8 (&kf)[8]) {
-    if (t0_ >= slab_end) return;
-    const int64_t pb = (((int64_t)pt[t0_ >> log2_ps] * Hkv + h) * ps) * hd;
-    const int tA = t0_ + lr, tB = t0_ + 16 + lr;
-    const int64_t oA = pb + (int64_t)(tA & (ps - 1)) * hd;
-    const int64_t oB = pb + (int64_t)(tB & (ps - 1)) * hd;
-    const bool vA = tA < slab_end, vB = tB < slab_end;
+  // Uniform tile count across the waves, as in paged_decode_mfma.
+  for (int ti = 0; ti < kSlab / 32; ti++) {
+    const int t0 = slab_start + ti * 32;
+    if (t0 < slab_end) {
+      const int64_t pb = (((int64_t)pt[t0 >> log2_ps] * Hkv + h) * ps) * hd;
+      // ---- K fragments (tokens t0+lr and t0+16+lr) and V staging rows ----
+      short8 kf[8], vf[8];
+      {
+        const int tA = t0 + lr, tB = t0 + 16 + lr;
+        const int64_t oA = pb + (int64_t)(tA & (ps - 1)) * hd;
+        const int64_t oB = pb + (int64_t)(tB & (ps - 1)) * hd;
+        const bool vA = tA < slab_end, vB = tB < slab_end;
 #pragma unroll
-    for (int kc = 0; kc < 4; kc++) {
-      kf[kc] = vA ? ld8(kcache, oA + kc * 32 + lg * 8) : short8{};
-      kf[4 + kc] = vB ? ld8(kcache, oB + kc * 32 + lg * 8) : short8{};
-    }
-  };
-  auto load_v = [&](int t0_, short8 (&vf)[8]) {
-    if (t0_ >= slab_end) return;
-    const int64_t pb = (((int64_t)pt[t0_ >> log2_ps] * Hkv + h) * ps) * hd;
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      const int unit = lane + u * 64;
-      const int d8 = unit & 15;
-      const int tg = unit >> 4;
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int t = t0_ + tg * 4 + j;
-        vf[u * 4 + j] = (t < slab_end)
-            ? ld8(vcache, pb + (int64_t)(t & (ps - 1)) * hd + d8 * 8)
-            : short8{};
+        for (int kc = 0; kc < 4; kc++) {
+          kf[kc] = vA ? ld8<FP8, 0>(kcache, oA + kc * 32 + lg * 8) : short8{};
+          kf[4 + kc] = vB ? ld8<FP8, 0>(kcache, oB + kc * 32 + lg * 8)
+                          : short8{};
+        }
       }
-    }
-  };
-  auto load_vt = [&](int t0_, short8 (&vf)[8]) {
-    const int64_t pb = (((int64_t)pt[t0_ >> log2_ps] * Hkv + h) * ps) * hd;
-    const int tin = t0_ & (ps - 1);
+      // unit = (8-dim chunk d8, 4-token group tg); 128 units per tile
 #pragma unroll
-    for (int da = 0; da < 8; da++) {
-      const int vrow = da * 16 + lr;
-      vf[da] = ld8(vcache, pb + (int64_t)vrow * ps + tin + lg * 8);
-    }
-    // boundary tile: zero tokens past slab_end (page tails can hold
-    // stale NaN/Inf bits; P=0 alone does not mask NaN * 0)
-    const int rem = slab_end - t0_;
-    if (rem < 32) {
+      for (int u = 0; u < 2; u++) {
+        const int unit = lane + u * 64;
+        const int d8 = unit & 15;
+        const int tg = unit >> 4;
 #pragma unroll
-      for (int da = 0; da < 8; da++)
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-          if (lg * 8 + j >= rem) vf[da][j] = 0;
-    }
-  };
-  auto store_v = [&](const short8 (&vf)[8]) {
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      const int unit = lane + u * 64;
-      const int d8 = unit & 15;
-      const int tg = unit >> 4;
-#pragma unroll
-      for (int i = 0; i < 8; i++) {
-        const int d = d8 * 8 + i;
-        short4v pk = {vf[u * 4 + 0][i], vf[u * 4 + 1][i],
-                      vf[u * 4 + 2][i], vf[u * 4 + 3][i]};
-        const int toff = XK2 ? ((tg * 8) ^ (((d >> 4) & 1) << 5)) : (tg * 8);
-        *reinterpret_cast<short4v*>((char*)v_lds + d * VS + toff) = pk;
+        for (int j = 0; j < 4; j++) {
+          const int t = t0 + tg * 4 + j;
+          vf[u * 4 + j] = (t < slab_end)
+              ? ld8<FP8, 0>(vcache, pb + (int64_t)(t & (ps - 1)) * hd + d8 * 8)
+              : short8{};
+        }
       }
-    }
-  };
 
-  short8 kfr[2][8], vfr[2][8];
-  if constexpr (KPF) {
-    load_k(slab_start, kfr[0]);
-    load_v(slab_start, vfr[0]);
-  }
-
-  // VT-only tile compute (QK -> softmax -> P pack -> PV from registers):
-  // a specialization of the main-loop body below; keep the two in sync.
-  const float scale2 = scale * 1.44269504f;  // scale * log2(e)
-  auto tile_vt = [&](int t0, const short8 (&kf)[8], const short8 (&vf)[8]) {
-    f32x4 sA{0.f, 0.f, 0.f, 0.f}, sB{0.f, 0.f, 0.f, 0.f};
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kc = 0; kc < 4; kc++) {
-      short8 ka = kf[kc];
-      sA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-          *reinterpret_cast<bf16x8_t*>(&ka), q_frag[kc], sA, 0, 0, 0);
-    }
-    if (t0 + 16 < slab_end) {
+      // ---- S^T = K Q^T ----
+      f32x4 sA{0.f, 0.f, 0.f, 0.f}, sB{0.f, 0.f, 0.f, 0.f};
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int kc = 0; kc < 4; kc++) {
-        short8 kb2 = kf[4 + kc];
-        sB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            *reinterpret_cast<bf16x8_t*>(&kb2), q_frag[kc], sB, 0, 0, 0);
+        short8 ka = kf[kc];
+        sA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            *reinterpret_cast<bf16x8_t*>(&ka), q_frag[kc], sA, 0, 0, 0);
       }
-    }
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-    float pA[4], pB[4];
-    float mt = kNegInf;
-    if constexpr (LG2) {
-      // raw (unscaled) values; max commutes with the positive scale
-      const bool tail = t0 + 32 > slab_end;
-      if (!tail) {
+      if (t0 + 16 < slab_end) {
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-          pA[r] = sA[r];
-          pB[r] = sB[r];
-          mt = fmaxf(mt, fmaxf(pA[r], pB[r]));
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int tokA = t0 + lg * 4 + r, tokB = t0 + 16 + lg * 4 + r;
-          pA[r] = (tokA < slab_end) ? sA[r] : kNegInf;
-          pB[r] = (tokB < slab_end) ? sB[r] : kNegInf;
-          mt = fmaxf(mt, fmaxf(pA[r], pB[r]));
+        for (int kc = 0; kc < 4; kc++) {
+          short8 kb2 = kf[4 + kc];
+          sB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              *reinterpret_cast<bf16x8_t*>(&kb2), q_frag[kc], sB, 0, 0, 0);
         }
       }
-      mt = fmaxf(mt, __shfl_xor(mt, 16, WAVE_SIZE));
-      mt = fmaxf(mt, __shfl_xor(mt, 32, WAVE_SIZE));
-      const float mts = (mt <= kNegInf * 0.5f) ? kNegInf : mt * scale2;
-      const float thr = DEFER ? 8.0f * 1.44269504f : 0.0f;
-      if (mts > m_run + thr) {
-        const float corr =
-            (m_run <= kNegInf * 0.5f) ? 0.f : __builtin_amdgcn_exp2f(m_run - mts);
-        l_run *= corr;
+      __builtin_amdgcn_s_setprio(0);
+
+      // ---- stage V^T (packed transpose writes, swizzled slots) ----
 #pragma unroll
-        for (int d = 0; d < 8; d++) acc[d] *= corr;
-        m_run = mts;
-      }
-      float psum = 0.f;
+      for (int u = 0; u < 2; u++) {
+        const int unit = lane + u * 64;
+        const int d8 = unit & 15;
+        const int tg = unit >> 4;
 #pragma unroll
-      for (int r = 0; r < 4; r++) {
-        pA[r] = (pA[r] > kNegInf * 0.5f)
-                    ? __builtin_amdgcn_exp2f(fmaf(pA[r], scale2, -m_run)) : 0.f;
-        pB[r] = (pB[r] > kNegInf * 0.5f)
-                    ? __builtin_amdgcn_exp2f(fmaf(pB[r], scale2, -m_run)) : 0.f;
-        psum += pA[r] + pB[r];
+        for (int i = 0; i < 8; i++) {
+          const int d = d8 * 8 + i;
+          short4v pk = {vf[u * 4 + 0][i], vf[u * 4 + 1][i],
+                        vf[u * 4 + 2][i], vf[u * 4 + 3][i]};
+          const int toff = (tg * 8) ^ (((d >> 4) & 1) << 5);
+          *reinterpret_cast<short4v*>((char*)v_lds + d * kVStride + toff) = pk;
+        }
       }
-      psum += __shfl_xor(psum, 16, WAVE_SIZE);
-      psum += __shfl_xor(psum, 32, WAVE_SIZE);
-      l_run += psum;
-    } else {
+
+      // ---- softmax: rows are TOKENS (lg*4+r, +16 for the B tile), the
+      // lane's column is head lr; token-reduction = 8-reg fold + 2 shfls.
+      // (Not shared with the 64-token kernel: this one sums pA[r] + pB[r]
+      // per r, that one sums tile-major.)
+      float pA[4], pB[4];
+      float mt = kNegInf;
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const int tokA = t0 + lg * 4 + r, tokB = t0 + 16 + lg * 4 + r;
@@ -924,16 +849,7 @@ __global__ __launch_bounds__(kBlock, MINW) void paged_decode_mfma_swapped(
         pB[r] = (tokB < slab_end) ? sB[r] * scale : kNegInf;
         mt = fmaxf(mt, fmaxf(pA[r], pB[r]));
       }
-      mt = fmaxf(mt, __shfl_xor(mt, 16, WAVE_SIZE));
-      mt = fmaxf(mt, __shfl_xor(mt, 32, WAVE_SIZE));
-      const float thr = DEFER ? 8.0f : 0.0f;
-      if (mt > m_run + thr) {
-        const float corr = (m_run <= kNegInf * 0.5f) ? 0.f : __expf(m_run - mt);
-        l_run *= corr;
-#pragma unroll
-        for (int d = 0; d < 8; d++) acc[d] *= corr;
-        m_run = mt;
-      }
+      swapped_update_max(mt, m_run, l_run, acc);
       float psum = 0.f;
 #pragma unroll
       for (int r = 0; r < 4; r++) {
@@ -944,37 +860,178 @@ __global__ __launch_bounds__(kBlock, MINW) void paged_decode_mfma_swapped(
       psum += __shfl_xor(psum, 16, WAVE_SIZE);
       psum += __shfl_xor(psum, 32, WAVE_SIZE);
       l_run += psum;
-    }
-    auto cvtpk = [](float a, float bb) {
-      unsigned int r;
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(bb));
-      return r;
-    };
-    const unsigned int A0 = cvtpk(pA[0], pA[1]), A1 = cvtpk(pA[2], pA[3]);
-    const unsigned int B0 = cvtpk(pB[0], pB[1]), B1 = cvtpk(pB[2], pB[3]);
-    uint2_t s1 = __builtin_amdgcn_permlane32_swap(A0, B0, false, false);
-    uint2_t s2 = __builtin_amdgcn_permlane32_swap(A1, B1, false, false);
-    uint2_t f02 = __builtin_amdgcn_permlane16_swap(s1.x, s1.y, false, false);
-    uint2_t f13 = __builtin_amdgcn_permlane16_swap(s2.x, s2.y, false, false);
-    unsigned int w[4] = {f02.x, f13.x, f02.y, f13.y};
-    bf16x8_t p_frag = *reinterpret_cast<bf16x8_t*>(w);
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int da = 0; da < 8; da++) {
-      short8 va_s = vf[da];
-      acc[da] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-          *reinterpret_cast<bf16x8_t*>(&va_s), p_frag, acc[da], 0, 0, 0);
-    }
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-  };
+      const bf16x8_t p_frag = pack_p_frag(pA, pB);
 
-  // ---- VT3: 64-token tiles ----------------------------------------
-  // Rationale (PMC): at 32-token tiles the wave issues only 16 b128
-  // loads per compute batch, so load-issue duty caps effective BW at
-  // ~77% of the pattern ceiling (WAIT_ANY-dominated). 64-token tiles
-  // issue 32 loads back-to-back (2 KB in flight per wave) before the
-  // QK/softmax/PV batch. Single-buffered; MINW=2 keeps 2 waves/SIMD.
-  auto softmax_pack64 = [&](int t0, f32x4 (&sT)[4], bf16x8_t (&p_frag)[2]) {
+      // V staging for THIS tile must be visible (same wave, in-order LDS)
+      __builtin_amdgcn_wave_barrier();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+      // ---- PV: O^T[dim][head] += V^T[dim][tok] P^T[tok][head] ----
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int da = 0; da < 8; da++) {
+        const int vrow = da * 16 + lr;
+        const int vtoff = (lg * 16) ^ (((vrow >> 4) & 1) << 5);
+        short8 va_s = *reinterpret_cast<const short8*>(
+            (const char*)v_lds + vrow * kVStride + vtoff);
+        acc[da] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            *reinterpret_cast<bf16x8_t*>(&va_s), p_frag, acc[da], 0, 0, 0);
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
+    // back-edge fence: the next tile's staging writes must not be
+    // scheduled above this tile's outstanding LDS fragment reads
+    __builtin_amdgcn_wave_barrier();
+  }
+
+  swapped_merge_store(merge, acc, m_run, l_run, partial, ml, out, b, h, c, G,
+                      Hq, C, hd, wid, lr, lg);
+}
+
+// d-major V pages ([P, Hkv, hd, ps]: elem offset d * page_size + token
+// instead of token * hd + d), the "VT4" kernel. The PV A-fragment is then
+// ONE contiguous b128 global load and V needs no staging at all (the
+// transpose was the token-major kernel's VALU bottleneck, VALU:MFMA 28:1).
+// The write side pays ~32x DRAM amplification only for single-token decode
+// appends (~10 MB/step vs 22 GB/step of V reads); prefill appends cover
+// whole 64B lines in L2 before eviction.
+//   64-token tiles: at 32 tokens a wave issues only 16 b128 loads per
+//   compute batch and load-issue duty caps the bandwidth; 64-token tiles
+//   put 2 KB per wave in flight before the QK/softmax/PV batch.
+//   K through LDS: direct K B-fragment loads touch 16 rows x 64 B per
+//   instruction; instead the wave loads K in fully contiguous 1 KB bursts
+//   (4 rows x 256 B) and re-reads the fragments from its LDS region (8 KB,
+//   the region the token-major kernel stages V in). Two 32-token halves
+//   reuse the buffer; wave-local barriers only.
+// NT selects non-temporal K and V loads (see ld8).
+template <int FP8, int NT>
+__global__ __launch_bounds__(kBlock) void paged_decode_mfma_swapped_dmajor(
+    float* __restrict__ partial, float* __restrict__ ml,
+    short* __restrict__ out, const short* __restrict__ q,
+    const short* __restrict__ kcache, const short* __restrict__ vcache,
+    const int32_t* __restrict__ page_table, const int32_t* __restrict__ ctx_lens,
+    float scale, int chunk, int G, int B, int Hkv, int C, int max_pages,
+    int log2_ps, int hd) {
+  const int kSlab = chunk / 4;
+  const int b = blockIdx.x;
+  const int h = blockIdx.y;
+  const int c = blockIdx.z;
+  const int Hq = Hkv * G;
+  const int ctx = ctx_lens[b];
+  const int chunk_start = c * chunk;
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int lr = lane & 15;
+  const int lg = lane >> 4;
+  const int ps = 1 << log2_ps;
+
+  extern __shared__ float lds[];
+  float* merge = lds;                                   // 4*G*(hd+2)
+  short* q_lds_s = reinterpret_cast<short*>(merge + 4 * G * (hd + 2));
+  short* k_lds = q_lds_s + G * hd + wid * (hd * kVStride / 2);  // per-wave
+
+  if (chunk_start >= ctx) {
+    write_empty_chunk(ml, out, b, h, c, G, Hq, C, hd);
+    return;
+  }
+  stage_q(q_lds_s, q, b, h, G, Hq, hd);
+  bf16x8_t q_frag[4];
+  load_q_frag(q_frag, q_lds_s, G, hd, lr, lg);
+
+  float m_run = kNegInf, l_run = 0.f;
+  f32x4 acc[8];
+#pragma unroll
+  for (int d = 0; d < 8; d++) acc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int slab_start = chunk_start + wid * kSlab;
+  const int slab_end = min(slab_start + kSlab, ctx);
+  const int32_t* pt = page_table + (int64_t)b * max_pages;
+
+  // 32 tokens of K -> LDS [32 rows][256 B], 16 B chunks XOR-swizzled by
+  // row. Burst i covers rows {i*4 .. i*4+3} fully (lane>>4 = row, lane&15
+  // = 16B chunk). Uniform (no break-in-unroll): rows past slab_end clamp
+  // to the last valid token and are masked when read.
+  auto stage_k32 = [&](int tb32, short8 (&sreg)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const int tok = tb32 + i * 4 + (lane >> 4);
+      const int tsafe = tok < slab_end ? tok : slab_end - 1;
+      const int64_t pb =
+          (((int64_t)pt[tsafe >> log2_ps] * Hkv + h) * ps) * hd;
+      sreg[i] = ld8<FP8, NT>(
+          kcache, pb + (int64_t)(tsafe & (ps - 1)) * hd + (lane & 15) * 8);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const int row = i * 4 + (lane >> 4);
+      *reinterpret_cast<short8*>(
+          (char*)k_lds + row * 256 +
+          (((lane & 15) * 16) ^ ((row & 7) << 4))) = sreg[i];
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  };
+  // S^T tiles 2*half and 2*half+1 of the 64-token tile from the staged K
+  auto qk_half = [&](int t0, int half, f32x4 (&sT)[4]) {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int tg2 = 0; tg2 < 2; tg2++) {
+      const int tg = half * 2 + tg2;
+      f32x4 acc_s{0.f, 0.f, 0.f, 0.f};
+      if (t0 + tg * 16 < slab_end) {
+#pragma unroll
+        for (int kc = 0; kc < 4; kc++) {
+          const int row = tg2 * 16 + lr;
+          short8 ka = *reinterpret_cast<const short8*>(
+              (const char*)k_lds + row * 256 +
+              ((kc * 64 + lg * 16) ^ ((row & 7) << 4)));
+          const bool valid = t0 + tg * 16 + lr < slab_end;
+          if (!valid) ka = short8{};
+          acc_s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              *reinterpret_cast<bf16x8_t*>(&ka), q_frag[kc], acc_s, 0, 0, 0);
+        }
+      }
+      sT[tg] = acc_s;
+    }
+    __builtin_amdgcn_s_setprio(0);
+  };
+  // V^T fragments straight from the d-major pages: vf[da*2+tc] = dims
+  // da*16+lr, tokens t0 + tc*32 + lg*8 + 0..7. Uniform: a 32-token group
+  // fully past slab_end clamps its page to the last valid 32-block (safe
+  // memory) and rem <= 0 zeroes every element. Tokens past slab_end are
+  // zeroed because page tails can hold stale NaN/Inf bits and P = 0 alone
+  // does not mask NaN * 0.
+  auto load_v64 = [&](int t0_, short8 (&vf)[16]) {
+#pragma unroll
+    for (int tc = 0; tc < 2; tc++) {
+      const int tb = t0_ + tc * 32;
+      const int tlast = ((slab_end - 1) >> 5) << 5;  // last valid 32-block
+      const int tsafe = tb < slab_end ? tb : tlast;
+      const int64_t pb =
+          (((int64_t)pt[tsafe >> log2_ps] * Hkv + h) * ps) * hd;
+      const int tin = tsafe & (ps - 1);
+      const int rem = slab_end - tb;
+#pragma unroll
+      for (int da = 0; da < 8; da++) {
+        const int vrow = da * 16 + lr;
+        short8 v8 = ld8<FP8, NT>(vcache,
+                                 pb + (int64_t)vrow * ps + tin + lg * 8);
+        if (rem < 32) {
+#pragma unroll
+          for (int j = 0; j < 8; j++)
+            if (lg * 8 + j >= rem) v8[j] = 0;
+        }
+        vf[da * 2 + tc] = v8;
+      }
+    }
+  };
+  // Softmax over the four 16-token S^T tiles, P pack and PV from the V
+  // registers. Interior tiles skip the token masks. (Sums tile-major - see
+  // the token-major kernel.) Keep this a lambda like the three above: with
+  // the same statements written straight into the loop below, hipcc keeps
+  // the accumulators in VGPRs and copies all 32 to AGPRs every tile (34
+  // instructions more per tile; the nt sweep row measured 4 % slower).
+  auto softmax_pv64 = [&](int t0, f32x4 (&sT)[4], const short8 (&v64)[16]) {
     float pv[4][4];
     float mt = kNegInf;
     const bool tail = t0 + 64 > slab_end;
@@ -996,16 +1053,7 @@ __global__ __launch_bounds__(kBlock, MINW) void paged_decode_mfma_swapped(
           mt = fmaxf(mt, pv[tg][r]);
         }
     }
-    mt = fmaxf(mt, __shfl_xor(mt, 16, WAVE_SIZE));
-    mt = fmaxf(mt, __shfl_xor(mt, 32, WAVE_SIZE));
-    const float thr = DEFER ? 8.0f : 0.0f;
-    if (mt > m_run + thr) {
-      const float corr = (m_run <= kNegInf * 0.5f) ? 0.f : __expf(m_run - mt);
-      l_run *= corr;
-#pragma unroll
-      for (int d = 0; d < 8; d++) acc[d] *= corr;
-      m_run = mt;
-    }
+    swapped_update_max(mt, m_run, l_run, acc);
     float psum = 0.f;
 #pragma unroll
     for (int tg = 0; tg < 4; tg++)
@@ -1018,461 +1066,46 @@ __global__ __launch_bounds__(kBlock, MINW) void paged_decode_mfma_swapped(
     psum += __shfl_xor(psum, 16, WAVE_SIZE);
     psum += __shfl_xor(psum, 32, WAVE_SIZE);
     l_run += psum;
-    auto cvtpk = [](float a, float bb) {
-      unsigned int r;
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(bb));
-      return r;
-    };
-    // two 32-token PV B-frags, each combining two 16-token S tiles via
-    // the same cvt_pk + permlane swap network as the 32-token path
-#pragma unroll
-    for (int tc = 0; tc < 2; tc++) {
-      const float* pa = pv[tc * 2];
-      const float* pb = pv[tc * 2 + 1];
-      const unsigned int A0 = cvtpk(pa[0], pa[1]), A1 = cvtpk(pa[2], pa[3]);
-      const unsigned int B0 = cvtpk(pb[0], pb[1]), B1 = cvtpk(pb[2], pb[3]);
-      uint2_t s1 = __builtin_amdgcn_permlane32_swap(A0, B0, false, false);
-      uint2_t s2 = __builtin_amdgcn_permlane32_swap(A1, B1, false, false);
-      uint2_t f02 = __builtin_amdgcn_permlane16_swap(s1.x, s1.y, false, false);
-      uint2_t f13 = __builtin_amdgcn_permlane16_swap(s2.x, s2.y, false, false);
-      unsigned int w[4] = {f02.x, f13.x, f02.y, f13.y};
-      p_frag[tc] = *reinterpret_cast<bf16x8_t*>(w);
-    }
-  };
-  auto tile_vt64_post = [&](int t0, f32x4 (&sT)[4],
-                            const short8 (&vf)[16]) {
+    // two 32-token PV B-frags, each from two 16-token S^T tiles
     bf16x8_t p_frag[2];
-    softmax_pack64(t0, sT, p_frag);
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int tc = 0; tc < 2; tc++)
+      p_frag[tc] = pack_p_frag(pv[tc * 2], pv[tc * 2 + 1]);
+
+    // ---- PV from the V registers ----
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int da = 0; da < 8; da++)
 #pragma unroll
       for (int tc = 0; tc < 2; tc++) {
-        short8 va_s = vf[da * 2 + tc];
+        short8 va_s = v64[da * 2 + tc];
         acc[da] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             *reinterpret_cast<bf16x8_t*>(&va_s), p_frag[tc], acc[da], 0, 0, 0);
       }
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
   };
-  auto tile_vt64 = [&](int t0, const short8 (&kf)[16],
-                       const short8 (&vf)[16]) {
+
+  short8 v64[16], sreg[8];
+  for (int t0 = slab_start; t0 < slab_end; t0 += 64) {
     f32x4 sT[4];
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int tg = 0; tg < 4; tg++) {
-      f32x4 acc_s{0.f, 0.f, 0.f, 0.f};
-      if (t0 + tg * 16 < slab_end) {
-#pragma unroll
-        for (int kc = 0; kc < 4; kc++) {
-          short8 ka = kf[tg * 4 + kc];
-          acc_s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              *reinterpret_cast<bf16x8_t*>(&ka), q_frag[kc], acc_s, 0, 0, 0);
-        }
-      }
-      sT[tg] = acc_s;
-    }
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-    tile_vt64_post(t0, sT, vf);
-  };
-  auto load_k64 = [&](int t0_, short8 (&kf)[16]) {
-    // uniform (no break-in-unroll): groups past slab_end clamp their page
-    // lookup to the last valid token and mask values via vA
-#pragma unroll
-    for (int tg = 0; tg < 4; tg++) {
-      const int tb = t0_ + tg * 16;
-      const int tsafe = tb < slab_end ? tb : slab_end - 1;
-      const int64_t pb =
-          (((int64_t)pt[tsafe >> log2_ps] * Hkv + h) * ps) * hd;
-      const int tA = tb + lr;
-      const int64_t oA = pb + (int64_t)(tA & (ps - 1)) * hd;
-      const bool vA = tA < slab_end;
-#pragma unroll
-      for (int kc = 0; kc < 4; kc++)
-        kf[tg * 4 + kc] = vA ? ld8(kcache, oA + kc * 32 + lg * 8) : short8{};
-    }
-  };
-  auto load_v64 = [&](int t0_, short8 (&vf)[16]) {
-    // uniform: a 32-token group fully past slab_end clamps its page to the
-    // last valid 32-block (safe memory) and rem <= 0 zeroes every element
-#pragma unroll
-    for (int tc = 0; tc < 2; tc++) {
-      const int tb = t0_ + tc * 32;
-      const int tlast = ((slab_end - 1) >> 5) << 5;  // last valid 32-block
-      const int tsafe = tb < slab_end ? tb : tlast;
-      const int64_t pb =
-          (((int64_t)pt[tsafe >> log2_ps] * Hkv + h) * ps) * hd;
-      const int tin = tsafe & (ps - 1);
-      const int rem = slab_end - tb;
-#pragma unroll
-      for (int da = 0; da < 8; da++) {
-        const int vrow = da * 16 + lr;
-        short8 v8 = ld8(vcache, pb + (int64_t)vrow * ps + tin + lg * 8);
-        if (rem < 32) {
-#pragma unroll
-          for (int j = 0; j < 8; j++)
-            if (lg * 8 + j >= rem) v8[j] = 0;
-        }
-        vf[da * 2 + tc] = v8;
-      }
-    }
-  };
-
-  // ---- VT4: VT3 + K staged through per-wave LDS --------------------
-  // K's direct B-frag loads touch 16 rows x 64B per instruction (the
-  // 5.74 TB/s pattern); staging K cooperatively IN-WAVE with 4-row x
-  // 256B fully-contiguous 1KB bursts targets the 6.3 linear ceiling for
-  // half the kernel's bytes. Two 32-token halves reuse one 8 KB buffer
-  // per wave (block LDS stays under 2-resident at MINW=2); V loads stay
-  // direct (their rows are already 128B-contiguous).
-  auto stage_k32 = [&](int tb32, short* klds_w, short8 (&sreg)[8]) {
-    // 8 bursts: burst i covers rows {i*4 .. i*4+3} fully (lane>>4 = row,
-    // lane&15 = 16B chunk)
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const int tok = tb32 + i * 4 + (lane >> 4);
-      const int tsafe = tok < slab_end ? tok : slab_end - 1;
-      const int64_t pb =
-          (((int64_t)pt[tsafe >> log2_ps] * Hkv + h) * ps) * hd;
-      sreg[i] = ld8(kcache,
-                    pb + (int64_t)(tsafe & (ps - 1)) * hd + (lane & 15) * 8);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const int row = i * 4 + (lane >> 4);
-      *reinterpret_cast<short8*>(
-          (char*)klds_w + row * 256 +
-          (((lane & 15) * 16) ^ ((row & 7) << 4))) = sreg[i];
-    }
+    stage_k32(t0, sreg);          // K half A (tokens t0..t0+31)
+    load_v64(t0, v64);            // V loads overlap QK below
+    qk_half(t0, 0, sT);
     __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-  auto qk_half = [&](int t0, int half, const short* klds_w, f32x4 (&sT)[4]) {
-#pragma unroll
-    for (int tg2 = 0; tg2 < 2; tg2++) {
-      const int tg = half * 2 + tg2;
-      f32x4 acc_s{0.f, 0.f, 0.f, 0.f};
-      if (t0 + tg * 16 < slab_end) {
-#pragma unroll
-        for (int kc = 0; kc < 4; kc++) {
-          const int row = tg2 * 16 + lr;
-          short8 ka = *reinterpret_cast<const short8*>(
-              (const char*)klds_w + row * 256 +
-              ((kc * 64 + lg * 16) ^ ((row & 7) << 4)));
-          const bool valid = t0 + tg * 16 + lr < slab_end;
-          if (!valid) ka = short8{};
-          acc_s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              *reinterpret_cast<bf16x8_t*>(&ka), q_frag[kc], acc_s, 0, 0, 0);
-        }
-      }
-      sT[tg] = acc_s;
-    }
-  };
-
-  // ---- VT5: VT4 + V through the same LDS buffer, fully linear -------
-  // With ps == 64 every 64-token tile is page-aligned, so a (page, head)
-  // d-major V plane is 16 KB CONTIGUOUS. Stage it in two 8 KB dim-halves
-  // (dims [0,64) then [64,128)) with 1KB linear bursts, consuming each
-  // half with the matching PV da range (da 0-3 reads rows < 64).
-  auto stage_v_half = [&](int tb64, int dlo, short* klds_w) {
-    const int64_t pb =
-        (((int64_t)pt[tb64 >> log2_ps] * Hkv + h) * ps) * hd;
-    const int rem = slab_end - tb64;
-    short8 vreg[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-      vreg[i] = ld8(vcache, pb + (int64_t)dlo * ps + (i * 64 + lane) * 8);
-    if (rem < 64) {
-      const int tok0 = (lane & 7) * 8;
-#pragma unroll
-      for (int i = 0; i < 8; i++)
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-          if (tok0 + j >= rem) vreg[i][j] = 0;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const int row = i * 8 + (lane >> 3);
-      *reinterpret_cast<short8*>(
-          (char*)klds_w + row * 128 +
-          ((((lane & 7)) * 16) ^ (((row ^ (row >> 3)) & 7) << 4))) = vreg[i];
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-  auto pv_half = [&](int dabase, const short* klds_w,
-                     const bf16x8_t (&p_frag)[2]) {
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int dl = 0; dl < 4; dl++)
-#pragma unroll
-      for (int tc = 0; tc < 2; tc++) {
-        const int row = dl * 16 + lr;
-        short8 va_s = *reinterpret_cast<const short8*>(
-            (const char*)klds_w + row * 128 +
-            ((tc * 64 + lg * 16) ^ (((row ^ (row >> 3)) & 7) << 4)));
-        acc[dabase + dl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            *reinterpret_cast<bf16x8_t*>(&va_s), p_frag[tc],
-            acc[dabase + dl], 0, 0, 0);
-      }
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-  };
-
-  if constexpr (VT == 5) {
-    short* klds_w = v_lds;
-    short8 sreg[8];
-    for (int t0 = slab_start; t0 < slab_end; t0 += 64) {
-      f32x4 sT[4];
-      stage_k32(t0, klds_w, sreg);
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-      qk_half(t0, 0, klds_w, sT);
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_wave_barrier();
-      stage_k32(t0 + 32, klds_w, sreg);
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-      qk_half(t0, 1, klds_w, sT);
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-      bf16x8_t p_frag[2];
-      softmax_pack64(t0, sT, p_frag);
-      __builtin_amdgcn_wave_barrier();
-      stage_v_half(t0, 0, klds_w);
-      pv_half(0, klds_w, p_frag);
-      __builtin_amdgcn_wave_barrier();
-      stage_v_half(t0, 64, klds_w);
-      pv_half(4, klds_w, p_frag);
-      // back-edge fence: the NEXT tile's staging ds_writes must not be
-      // scheduled above this tile's outstanding LDS frag reads
-      __builtin_amdgcn_wave_barrier();
-    }
-  } else if constexpr (VT == 4) {
-    short* klds_w = v_lds;  // reuse the (otherwise unused) V-staging LDS
-    short8 v64[16], sreg[8];
-    for (int t0 = slab_start; t0 < slab_end; t0 += 64) {
-      f32x4 sT[4];
-      stage_k32(t0, klds_w, sreg);          // K half A (tokens t0..t0+31)
-      load_v64(t0, v64);                    // V loads overlap QK below
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-      qk_half(t0, 0, klds_w, sT);
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_wave_barrier();
-      stage_k32(t0 + 32, klds_w, sreg);     // K half B overwrites A
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-      qk_half(t0, 1, klds_w, sT);
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-      tile_vt64_post(t0, sT, v64);
-      __builtin_amdgcn_wave_barrier();  // back-edge fence (see VT5)
-    }
-  } else if constexpr (VT == 3) {
-    short8 k64[16], v64[16];
-    for (int t0 = slab_start; t0 < slab_end; t0 += 64) {
-      load_k64(t0, k64);
-      load_v64(t0, v64);
-      tile_vt64(t0, k64, v64);
-    }
-  } else if constexpr (VT == 2) {
-    // software-pipelined: tile i+1's K/V global loads are in flight while
-    // tile i computes; two compile-time register sets (no runtime
-    // indexing -> no scratch spill, unlike KPF)
-    short8 kA[8], vA[8], kB[8], vB[8];
-    const int ntiles = kSlab / 32;
-    if (slab_start < slab_end) {
-      load_k(slab_start, kA);
-      load_vt(slab_start, vA);
-    }
-    for (int ti = 0; ti < ntiles; ti += 2) {
-      const int t0 = slab_start + ti * 32;
-      const int t1 = t0 + 32;
-      if (t1 < slab_end) {
-        load_k(t1, kB);
-        load_vt(t1, vB);
-      }
-      if (t0 < slab_end) tile_vt(t0, kA, vA);
-      const int t2 = t0 + 64;
-      if (t2 < slab_end) {
-        load_k(t2, kA);
-        load_vt(t2, vA);
-      }
-      if (t1 < slab_end) tile_vt(t1, kB, vB);
-    }
-  } else {
-  for (int ti = 0; ti < kSlab / 32; ti++) {
-    const int t0 = slab_start + ti * 32;
-    const bool active = t0 < slab_end;
-    const int cur = ti & 1;
-    f32x4 sA{0.f, 0.f, 0.f, 0.f}, sB{0.f, 0.f, 0.f, 0.f};
-    if constexpr (!KPF) {
-      if (active) {
-        load_k(t0, kfr[0]);
-        if constexpr (VT) load_vt(t0, vfr[0]);
-        else load_v(t0, vfr[0]);
-      }
-    }
-    const short8(&kf)[8] = KPF ? kfr[cur] : kfr[0];
-    const short8(&vf)[8] = KPF ? vfr[cur] : vfr[0];
-    if (active) {
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int kc = 0; kc < 4; kc++) {
-        short8 ka = kf[kc];
-        sA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            *reinterpret_cast<bf16x8_t*>(&ka), q_frag[kc], sA, 0, 0, 0);
-      }
-      if (t0 + 16 < slab_end) {
-#pragma unroll
-        for (int kc = 0; kc < 4; kc++) {
-          short8 kb2 = kf[4 + kc];
-          sB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              *reinterpret_cast<bf16x8_t*>(&kb2), q_frag[kc], sB, 0, 0, 0);
-        }
-      }
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-      // stage THIS tile's V rows (loaded last iteration under KPF);
-      // VT reads V^T fragments straight from global - nothing to stage
-      if constexpr (!VT) store_v(vf);
-      if constexpr (KPF) {
-        // issue next tile's K/V global loads now: their latency hides
-        // under this tile's softmax + PV
-        load_k(t0 + 32, kfr[cur ^ 1]);
-        load_v(t0 + 32, vfr[cur ^ 1]);
-      }
-    }
-
-    if (active) {
-      // ---- softmax: rows are TOKENS (lg*4+r, +16 for the B tile), the
-      // lane's column is head lr; token-reduction = 8-reg fold + 2 shfls
-      float pA[4], pB[4];
-      float mt = kNegInf;
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int tokA = t0 + lg * 4 + r, tokB = t0 + 16 + lg * 4 + r;
-        pA[r] = (tokA < slab_end) ? sA[r] * scale : kNegInf;
-        pB[r] = (tokB < slab_end) ? sB[r] * scale : kNegInf;
-        mt = fmaxf(mt, fmaxf(pA[r], pB[r]));
-      }
-      mt = fmaxf(mt, __shfl_xor(mt, 16, WAVE_SIZE));
-      mt = fmaxf(mt, __shfl_xor(mt, 32, WAVE_SIZE));
-      const float thr = DEFER ? 8.0f : 0.0f;
-      if (mt > m_run + thr) {
-        const float corr = (m_run <= kNegInf * 0.5f) ? 0.f
-                                                     : __expf(m_run - mt);
-        l_run *= corr;
-#pragma unroll
-        for (int d = 0; d < 8; d++) acc[d] *= corr;
-        m_run = mt;
-      }
-      float psum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        pA[r] = (pA[r] > kNegInf * 0.5f) ? __expf(pA[r] - m_run) : 0.f;
-        pB[r] = (pB[r] > kNegInf * 0.5f) ? __expf(pB[r] - m_run) : 0.f;
-        psum += pA[r] + pB[r];
-      }
-      psum += __shfl_xor(psum, 16, WAVE_SIZE);
-      psum += __shfl_xor(psum, 32, WAVE_SIZE);
-      l_run += psum;
-
-      // ---- P^T -> PV B-fragment in registers (4 cvt_pk + 4 swaps) ----
-      auto cvtpk = [](float a, float bb) {
-        unsigned int r;
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(bb));
-        return r;
-      };
-      const unsigned int A0 = cvtpk(pA[0], pA[1]), A1 = cvtpk(pA[2], pA[3]);
-      const unsigned int B0 = cvtpk(pB[0], pB[1]), B1 = cvtpk(pB[2], pB[3]);
-      uint2_t s1 = __builtin_amdgcn_permlane32_swap(A0, B0, false, false);
-      uint2_t s2 = __builtin_amdgcn_permlane32_swap(A1, B1, false, false);
-      uint2_t f02 = __builtin_amdgcn_permlane16_swap(s1.x, s1.y, false, false);
-      uint2_t f13 = __builtin_amdgcn_permlane16_swap(s2.x, s2.y, false, false);
-      unsigned int w[4] = {f02.x, f13.x, f02.y, f13.y};
-      bf16x8_t p_frag = *reinterpret_cast<bf16x8_t*>(w);
-
-      if constexpr (!VT) {
-        // V staging for THIS tile must be visible (same wave, in-order LDS)
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-
-      // ---- PV: O^T[dim][head] += V^T[dim][tok] P^T[tok][head] ----
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int da = 0; da < 8; da++) {
-        short8 va_s;
-        if constexpr (VT) {
-          va_s = vf[da];
-        } else {
-          const int vrow = da * 16 + lr;
-          const int vtoff = XK2 ? ((lg * 16) ^ (((vrow >> 4) & 1) << 5))
-                                : (lg * 16);
-          va_s = *reinterpret_cast<const short8*>(
-              (const char*)v_lds + vrow * VS + vtoff);
-        }
-        acc[da] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            *reinterpret_cast<bf16x8_t*>(&va_s), p_frag, acc[da], 0, 0, 0);
-      }
-      if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-    }
+    stage_k32(t0 + 32, sreg);     // K half B overwrites A
+    qk_half(t0, 1, sT);
+    softmax_pv64(t0, sT, v64);
+    // back-edge fence: the NEXT tile's staging ds_writes must not be
+    // scheduled above this tile's outstanding LDS frag reads
     __builtin_amdgcn_wave_barrier();
   }
-  }  // VT != 2
 
-  // ---- cross-wave merge: acc[da][r] is O^T[dim da*16+lg*4+r][head lr]
-  __syncthreads();
-  float* my = merge + wid * G * (hd + 2);
-  if (lr < G) {
-#pragma unroll
-    for (int da = 0; da < 8; da++)
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-        my[lr * (hd + 2) + da * 16 + lg * 4 + r] = acc[da][r];
-    if (lg == 0) {
-      my[lr * (hd + 2) + hd] = m_run;
-      my[lr * (hd + 2) + hd + 1] = l_run;
-    }
-  }
-  __syncthreads();
-
-  for (int i = threadIdx.x; i < G * hd; i += kBlock) {
-    const int g = i / hd;
-    const int d = i % hd;
-    float mw[4], lw[4];
-    float mstar = kNegInf;
-#pragma unroll
-    for (int w2 = 0; w2 < 4; w2++) {
-      mw[w2] = merge[w2 * G * (hd + 2) + g * (hd + 2) + hd];
-      lw[w2] = merge[w2 * G * (hd + 2) + g * (hd + 2) + hd + 1];
-      mstar = fmaxf(mstar, mw[w2]);
-    }
-    float lsum = 0.f, asum = 0.f;
-#pragma unroll
-    for (int w2 = 0; w2 < 4; w2++) {
-      const float corr = (lw[w2] > 0.f) ? __expf(mw[w2] - mstar) : 0.f;
-      lsum += lw[w2] * corr;
-      asum += merge[w2 * G * (hd + 2) + g * (hd + 2) + d] * corr;
-    }
-    const int qh = h * G + g;
-    if (C == 1) {
-      out[((int64_t)b * Hq + qh) * hd + d] =
-          f32_to_bf16(lsum > 0.f ? asum / lsum : 0.f);
-    } else {
-      partial[(((int64_t)b * Hq + qh) * C + c) * hd + d] = asum;
-      if (d == 0) {
-        float* mlp = ml + (((int64_t)b * Hq + qh) * C + c) * 2;
-        mlp[0] = mstar; mlp[1] = lsum;
-      }
-    }
-  }
-  if (C > 1 && chunk_cnt != nullptr) {
-    __syncthreads();  // all merge-loop writes of this block done
-    fused_merge();
-  }
+  swapped_merge_store(merge, acc, m_run, l_run, partial, ml, out, b, h, c, G,
+                      Hq, C, hd, wid, lr, lg);
 }
 
-// VT layout needs no V staging LDS: merge + q only
-inline int mfma_swapped_vt_lds_bytes(int G, int hd) {
-  return 4 * G * (hd + 2) * 4 + G * hd * 2;
-}
-
-inline int mfma_swapped_lds_bytes(int G, int hd, int vs = 80) {
-  return 4 * G * (hd + 2) * 4 + G * hd * 2 + 4 * hd * vs;  // no P tile
+inline int mfma_swapped_lds_bytes(int G, int hd) {
+  return 4 * G * (hd + 2) * 4 + G * hd * 2 + 4 * hd * kVStride;  // no P tile
 }
 
 // Phase 2: merge chunk partials. grid (B, Hq), block = 128.

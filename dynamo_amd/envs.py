@@ -30,11 +30,6 @@ ENV_VARS = {
     "DYNAMO_DECODE_CHUNK": "decode attention context-chunk tokens override",
     "DYNAMO_DECODE_MFMA": "0 = force the VALU decode path (token-major only)",
     "DYNAMO_DECODE_SWAPPED": "0 = A-operand MFMA decode (token-major only)",
-    "DYNAMO_VT3_VARIANT":
-        "d-major decode variant select: 0=VT4 (default), 1=VT3, 2=VT2, "
-        "5=VT5 (recorded-negative V-LDS variant)",
-    "DYNAMO_FUSED_MERGE":
-        "1 = fused decode chunk merge (recorded-negative; threadfence cost)",
     "DYNAMO_DECODE_NT":
         "1 = non-temporal K/V loads in the d-major (VT4) decode attention "
         "kernel (bit-identical outputs; recorded-negative, slower)",
