@@ -176,6 +176,43 @@ def bench_sampling_decode(B=16, V=128256):
                      lambda fast: ops.hip().greedy_sample(out, logits, fast))
 
 
+def bench_logit_processors(B=16, V=128256):
+    """logits_process with every row penalised, as the decode graph's
+    neighbour runs it (timeit_graph), against the 12 B per vocabulary entry
+    of its contract (logits read + write, counts read), and the greedy
+    kernel (4 B per entry) at the same shape as the yardstick. `sparse`: each
+    row has seen 2048 prompt and 512 output tokens, so most 16-byte logits
+    vectors are not written back; `dense`: every token seen, every vector
+    written; `+min_p` adds the max and mask passes over the row."""
+    logits = torch.randn(B, V, device="cuda")
+    slots = torch.arange(B, dtype=torch.int32, device="cuda")
+    sparse = torch.zeros(B, V, dtype=torch.int32, device="cuda")
+    for b in range(B):
+        sparse[b, torch.randint(0, V, (2048,), device="cuda")] = 1
+        sparse[b, torch.randint(0, V, (512,), device="cuda")] += 2
+    dense = torch.full((B, V), 3, dtype=torch.int32, device="cuda")
+    gb = B * V * 12 / 1e9
+    for name, bank, p in (("sparse", sparse, (1.1, 0.1, 0.1, 0.0, 1.0)),
+                          ("dense", dense, (1.1, 0.1, 0.1, 0.0, 1.0)),
+                          ("dense+min_p", dense, (1.1, 0.1, 0.1, 0.05, 1.0))):
+        params = torch.tensor([p] * B, dtype=torch.float32, device="cuda")
+        ts = {False: [], True: []}
+        for _ in range(3):
+            for fast in (False, True):
+                work = logits.clone()
+                ts[fast].append(timeit_graph(
+                    lambda: ops.hip().logits_process(
+                        work, bank, slots, params, None, None, None, fast)))
+        g, f = min(ts[False]), min(ts[True])
+        print(f"logits_process [B{B} V{V}] {name:12s}: scalar {g*1e6:7.2f} us "
+              f"| vector {f*1e6:7.2f} us  {gb/f:7.1f} GB/s of 12 B/entry")
+    out = torch.empty(B, dtype=torch.int32, device="cuda")
+    t = min(timeit_graph(lambda: ops.hip().greedy_sample(out, logits, True))
+            for _ in range(3))
+    print(f"greedy         [B{B} V{V}]             : vector {t*1e6:7.2f} us  "
+          f"{B * V * 4 / 1e9 / t:7.1f} GB/s of 4 B/entry")
+
+
 def bench_gemm(M=16, K=8192, N=8192):
     a = torch.randn(M, K, dtype=torch.bfloat16, device="cuda")
     w = torch.randn(N, K, dtype=torch.bfloat16, device="cuda")
@@ -387,6 +424,9 @@ if __name__ == "__main__":
         bench_rope_append()
         bench_rope_append(T=8192)
         bench_sampling_decode()
+    if w in ("all", "logits"):
+        bench_logit_processors(B=16)
+        bench_logit_processors(B=64)
     if w in ("all", "gemm"):
         bench_gemm()
         bench_gemm(M=8192)

@@ -54,6 +54,14 @@ void topkp_sample(torch::Tensor out, torch::Tensor logits,
 void gumbel_sample(torch::Tensor out, torch::Tensor logits, torch::Tensor inv_temp,
                    int64_t seed, c10::optional<torch::Tensor> row_seeds,
                    bool allow_fast);
+// logits_process.hip
+void penalty_fold(torch::Tensor counts, torch::Tensor slot,
+                  torch::Tensor token, torch::Tensor is_prompt);
+void logits_process(torch::Tensor logits, c10::optional<torch::Tensor> counts,
+                    torch::Tensor slot, torch::Tensor params,
+                    c10::optional<torch::Tensor> bias_off,
+                    c10::optional<torch::Tensor> bias_ids,
+                    c10::optional<torch::Tensor> bias_vals, bool allow_fast);
 // skinny_gemm.hip
 void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                  int64_t wpb, int64_t u, int64_t nt, bool nontemporal,
@@ -135,6 +143,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topkp_sample", &topkp_sample, py::arg("out"), py::arg("logits"),
         py::arg("inv_temp"), py::arg("top_k"), py::arg("top_p"),
         py::arg("seed"), py::arg("row_seeds") = py::none());
+  // per-request logit processors, in place on fp32 logits [B, V]. counts
+  // [S, V] int32: bit 0 = token is in the prompt, bits 1.. = its count in the
+  // output; slot [B] (-1 = no bank row); params [B, 5] = repetition, presence,
+  // frequency, min_p, temperature; bias as CSR over rows. penalty_fold adds
+  // entry i (slot, token, is_prompt) to the bank and skips ids out of range
+  m.def("penalty_fold", &penalty_fold, py::arg("counts"), py::arg("slot"),
+        py::arg("token"), py::arg("is_prompt"));
+  m.def("logits_process", &logits_process, py::arg("logits"),
+        py::arg("counts"), py::arg("slot"), py::arg("params"),
+        py::arg("bias_off") = py::none(), py::arg("bias_ids") = py::none(),
+        py::arg("bias_vals") = py::none(), py::arg("allow_fast") = true);
   // y = x @ w^T for 1 <= M <= 16 (decode); raises on anything the kernel
   // does not handle - dispatch and fallback live in ops.linear
   m.def("skinny_gemm", &skinny_gemm, py::arg("y"), py::arg("x"), py::arg("w"),

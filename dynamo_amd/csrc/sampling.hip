@@ -5,9 +5,12 @@
 //   argmax(logits/T + G_i), G_i = -log(-log(U_i)) with a counter-based
 //   in-kernel hash RNG (deterministic given seed; no host noise tensor).
 // Both are single-pass, vectorized, one workgroup per sequence.
+// top-k / top-p: one fused kernel, per-row thresholds by bisection, then the
+//   same Gumbel argmax over the surviving set (topkp_sample_kernel below).
 //
 // Capability parity: the reference delegates sampling to its engines; this
-// is the native path (top-p/top-k currently handled at the Python layer).
+// is the native path. Penalties, logit_bias and min_p edit the logits before
+// any of these kernels runs (logits_process.hip).
 #include "common.h"
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>

@@ -16,6 +16,7 @@ from dynamo_amd.models.layers import TPContext
 from .config import EngineConfig
 from .kv_cache import KvEvent, PageAllocator
 from .model_runner import ModelRunner
+from .penalties import PenaltyBank, validate_request
 from .scheduler import Request, ReqState, SamplingParams, Scheduler
 
 
@@ -85,6 +86,11 @@ class LLMEngine:
             self.graph_runner = GraphRunner(self.runner, cfg.max_num_seqs,
                                             use_graphs=use_graphs)
         self._last_sampled = None
+        # logit penalties: the count bank is allocated by the first request
+        # that needs it, so KV pool sizing does not see it
+        self.penalties = PenaltyBank(cfg.max_num_seqs)
+        if hasattr(self.runner, "penalties"):
+            self.runner.penalties = self.penalties
         self._lora = None
         self._puller = None   # disagg decode-side KvPuller (lazy)
         self._last_weight_delta_count = 0
@@ -169,6 +175,9 @@ class LLMEngine:
             slot = bank.slot(lora)
         if prompt_embeds is not None and not prompt_tokens:
             prompt_tokens = [0] * prompt_embeds.shape[0]
+        if sampling is not None and sampling.has_logit_processors:
+            validate_request(sampling, prompt_tokens,
+                             self.cfg.model.vocab_size)
         req = Request(req_id, prompt_tokens, sampling or SamplingParams())
         req.lora, req.lora_slot = lora, slot
         req.prompt_embeds = prompt_embeds
@@ -178,7 +187,9 @@ class LLMEngine:
 
     def abort(self, req_id: str):
         self.scheduler.abort(req_id)
-        self.requests.pop(req_id, None)
+        req = self.requests.pop(req_id, None)
+        if req is not None:
+            self.penalties.release(req)
 
     def has_work(self) -> bool:
         return self.scheduler.has_work()
@@ -231,6 +242,8 @@ class LLMEngine:
         with roctx_range("decode_step"):
             logits = gr.step(self._last_sampled)
         from .sampling import compute_logprobs, sample_tokens
+        # in place: the graph rewrites its logits buffer on every replay
+        self.penalties.process(logits, running)
         sampled = sample_tokens(logits, running, self.step_count)
         lps = compute_logprobs(logits, sampled, running)
         self._last_sampled = sampled
@@ -247,6 +260,7 @@ class LLMEngine:
             finished = reason is not None
             if finished:
                 finished_any = True
+                self.penalties.release(req)
                 if req.hold_kv:
                     req.state = ReqState.FINISHED
                     req.finish_reason = reason
@@ -284,6 +298,8 @@ class LLMEngine:
             self._last_sampled = None
         t0 = time.monotonic()
         sched = self.scheduler.schedule()
+        for req in sched.preempted:
+            self.penalties.release(req)
         if sched.is_empty:
             return []
         self.step_count += 1
@@ -307,6 +323,7 @@ class LLMEngine:
             reason = self._check_finish(req)
             finished = reason is not None
             if finished:
+                self.penalties.release(req)
                 hold = req.hold_kv if hasattr(req, "hold_kv") else False
                 if hold:
                     # keep pages alive for disagg transfer

@@ -84,6 +84,7 @@ class ModelRunner:
                                    v_transposed=self.v_transposed)
         self.num_pages = num_pages
         self.max_pages_per_seq = (cfg.max_model_len + cfg.page_size - 1) // cfg.page_size
+        self.penalties = None   # the engine's PenaltyBank (engine/penalties.py)
         self.decode_scratch = None
         if self.device.type == "cuda":
             self.decode_scratch = ops.DecodeScratch(
@@ -241,6 +242,8 @@ class ModelRunner:
         logits = self.model.compute_logits(rows)
         from .sampling import compute_logprobs, sample_tokens
         reqs = [s.req for s in sample_seqs]
+        if self.penalties is not None:
+            self.penalties.process(logits, reqs)
         sampled = sample_tokens(logits, reqs, step_seed)
         for r, lp in zip(reqs, compute_logprobs(logits, sampled, reqs)):
             r._logprobs = lp

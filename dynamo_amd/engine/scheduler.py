@@ -35,6 +35,38 @@ class SamplingParams:
     # top-N logprobs per generated token (0 = off); reference parity:
     # LLMEngineOutput log_probs/top_logprobs (protocols/common/llm_backend.rs)
     logprobs: int = 0
+    # logit processors (engine/penalties.py, csrc/logits_process.hip), applied
+    # to the fp32 logits in this order before sampling. Logprobs are reported
+    # from the processed logits.
+    #   repetition_penalty r != 1: l = l / r if l > 0 else l * r for every
+    #     token of the prompt or the output (HF/vLLM)
+    #   frequency_penalty, presence_penalty: l -= frequency * count +
+    #     presence for every token of the output so far (OpenAI)
+    #   logit_bias {token id: value}: l += value
+    #   min_p > 0, temperature T > 0: drop tokens whose probability under
+    #     softmax(l / T) is below min_p times the largest one
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    min_p: float = 0.0
+    logit_bias: Dict[int, float] = field(default_factory=dict)
+
+    def __post_init__(self):
+        # JSON and pickled-dict round trips (frontend, TP ranks, replay) turn
+        # the keys into strings: every holder sees ints
+        self.logit_bias = {int(k): float(v)
+                           for k, v in (self.logit_bias or {}).items()}
+
+    @property
+    def needs_counts(self) -> bool:
+        """Whether sampling needs the request's per-token counts."""
+        return (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
+                or self.frequency_penalty != 0.0)
+
+    @property
+    def has_logit_processors(self) -> bool:
+        return (self.needs_counts or bool(self.logit_bias)
+                or (self.min_p > 0.0 and self.temperature > 0.0))
 
 
 class ReqState(Enum):
@@ -79,6 +111,11 @@ class Request:
         # its slot in the engine's adapter bank; None / -1 = base model
         self.lora: Optional[str] = None
         self.lora_slot = -1
+        # logit penalties (engine/penalties.py): the request's row of the
+        # engine's count bank (-1 = none) and how many of all_tokens are
+        # folded into it
+        self.penalty_slot = -1
+        self.penalty_cursor = 0
 
     @property
     def has_embeds(self) -> bool:

@@ -14,7 +14,10 @@ still interoperate).
 LLM mapping (text in/out, matching the reference's ModelInput::Text):
   inputs:  "text_input" (BYTES, 1 string)  — the prompt
            "max_tokens" (INT32, optional), "temperature" (FP32, optional),
-           "top_p" (FP32), "top_k" (INT32), "seed" (INT64)
+           "top_p" (FP32), "top_k" (INT32), "seed" (INT64),
+           "repetition_penalty", "presence_penalty", "frequency_penalty",
+           "min_p" (FP32), "logit_bias" (BYTES, 1 JSON object
+           {token id: bias}); ranges as for the HTTP API
   outputs: "text_output" (BYTES, 1 string), "token_ids" (INT32, [n])
 """
 from __future__ import annotations
@@ -217,6 +220,31 @@ class KServeService:
             "seed": int(_scalar(tensors.get("seed"), 0)
                         if "seed" in tensors else 0),
         }
+        for k in ("repetition_penalty", "presence_penalty",
+                  "frequency_penalty", "min_p"):
+            if k in tensors:
+                v = _scalar(tensors[k])
+                if v is not None:
+                    sampling[k] = float(v)
+        if "logit_bias" in tensors:
+            import json
+            bc = list(tensors["logit_bias"].contents.bytes_contents)
+            try:
+                sampling["logit_bias"] = dict(json.loads(bc[0])) if bc else {}
+            except (ValueError, TypeError):
+                await context.abort(grpc.StatusCode.INVALID_ARGUMENT,
+                                    "logit_bias: not a JSON object")
+        from fastapi import HTTPException
+        from .openai import check_penalties
+        try:
+            check_penalties(
+                {k: v for k, v in sampling.items()
+                 if k in ("repetition_penalty", "presence_penalty",
+                          "frequency_penalty", "min_p", "logit_bias")},
+                ((entry.card or {}).get("model_config") or {}).get(
+                    "vocab_size"))
+        except HTTPException as e:
+            await context.abort(grpc.StatusCode.INVALID_ARGUMENT, e.detail)
         max_tokens = int(_scalar(tensors.get("max_tokens"), 128)
                          if "max_tokens" in tensors else 128)
         eos = getattr(entry.tokenizer, "eos_id", None)

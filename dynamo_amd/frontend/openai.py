@@ -13,7 +13,7 @@ import json
 import logging
 import time
 import uuid
-from typing import AsyncIterator, List, Optional, Union
+from typing import AsyncIterator, Dict, List, Optional, Union
 
 from fastapi import FastAPI, HTTPException, Request, WebSocket
 from fastapi.responses import JSONResponse, StreamingResponse
@@ -50,6 +50,13 @@ class CompletionRequest(BaseModel):
     seed: int = 0
     ignore_eos: bool = False
     logprobs: Optional[int] = None  # top-N logprobs per token
+    # logit processors (SamplingParams): None = the request template's value,
+    # else neutral. logit_bias maps token ids (JSON: strings) to [-100, 100]
+    repetition_penalty: Optional[float] = None
+    presence_penalty: Optional[float] = None
+    frequency_penalty: Optional[float] = None
+    min_p: Optional[float] = None
+    logit_bias: Optional[Dict[str, float]] = None
     # PreprocessedRequest prompt_embeds parity: {"b64", "shape", "dtype"}
     prompt_embeds: Optional[dict] = None
     user: Optional[str] = None      # sticky-session key
@@ -81,6 +88,13 @@ class ChatRequest(BaseModel):
     stop: Optional[Union[str, List[str]]] = None
     seed: int = 0
     ignore_eos: bool = False
+    # logit processors (SamplingParams): None = the request template's value,
+    # else neutral. logit_bias maps token ids (JSON: strings) to [-100, 100]
+    repetition_penalty: Optional[float] = None
+    presence_penalty: Optional[float] = None
+    frequency_penalty: Optional[float] = None
+    min_p: Optional[float] = None
+    logit_bias: Optional[Dict[str, float]] = None
     user: Optional[str] = None      # sticky-session key
     # next-turn KV warming (reference parity: preprocessor/
     # speculative_prefill.rs nvext.agent_hints.speculative_prefill): after
@@ -120,6 +134,41 @@ class ResponsesRequest(BaseModel):
     user: Optional[str] = None
 
 
+PENALTY_FIELDS = ("repetition_penalty", "presence_penalty",
+                  "frequency_penalty", "min_p", "logit_bias")
+
+
+def check_penalties(p: dict, vocab_size: Optional[int]):
+    """HTTP 400, naming the field, for a logit-processor value outside the
+    range the API documents (docs/OPERATIONS.md)."""
+    def bad(field, why):
+        raise HTTPException(400, f"{field}: {why}")
+
+    for k in ("presence_penalty", "frequency_penalty"):
+        if k in p and not -2.0 <= p[k] <= 2.0:
+            bad(k, f"must be in [-2, 2], got {p[k]}")
+    if "repetition_penalty" in p and not (
+            0.0 < p["repetition_penalty"] < float("inf")):
+        bad("repetition_penalty",
+            f"must be a finite number > 0, got {p['repetition_penalty']}")
+    if "min_p" in p and not 0.0 <= p["min_p"] <= 1.0:
+        bad("min_p", f"must be in [0, 1], got {p['min_p']}")
+    lb = p.get("logit_bias") or {}
+    if len(lb) > 300:
+        bad("logit_bias", f"at most 300 entries, got {len(lb)}")
+    for k, v in lb.items():
+        try:
+            tok = int(k)
+        except (TypeError, ValueError):
+            bad("logit_bias", f"key {k!r} is not a token id")
+        if tok < 0 or (vocab_size is not None and tok >= vocab_size):
+            bad("logit_bias", f"key {k!r} is not a token id below the "
+                              f"vocabulary size {vocab_size}")
+        if not -100.0 <= v <= 100.0:
+            bad("logit_bias", f"value for {k!r} must be in [-100, 100], "
+                              f"got {v}")
+
+
 def _session_of(req, raw: Request) -> Optional[str]:
     return raw.headers.get("x-session-id") or getattr(req, "user", None)
 
@@ -148,7 +197,7 @@ def build_app(manager: ModelManager,
               request_template: Optional[dict] = None) -> FastAPI:
     """request_template (reference parity: request_template.rs + the
     frontend --request-template flag): {"model", "temperature",
-    "max_completion_tokens"} defaults applied when a request omits the
+    "max_completion_tokens", and the logit-processor fields} defaults applied when a request omits the
     field; an explicit value always wins."""
     app = FastAPI(title="dynamo_amd", version="0.1.0")
     app.state.manager = manager
@@ -166,6 +215,24 @@ def build_app(manager: ModelManager,
         if getattr(req, "max_tokens", None) is not None:
             return req.max_tokens
         return int(tmpl.get("max_completion_tokens", 128))
+
+    def _penalties_of(req) -> dict:
+        """The logit-processor fields the request (else the template) sets."""
+        out = {}
+        for k in PENALTY_FIELDS:
+            v = getattr(req, k, None)
+            if v is None:
+                v = tmpl.get(k)
+            if v is not None:
+                out[k] = v
+        return out
+
+    def _check_penalties(entry, req):
+        p = _penalties_of(req)
+        if p:
+            vocab = ((entry.card or {}).get("model_config") or {}).get(
+                "vocab_size")
+            check_penalties(p, vocab)
 
     @app.get("/health")
     async def health():
@@ -194,6 +261,7 @@ def build_app(manager: ModelManager,
                     "top_k": getattr(req, "top_k", 0),
                     "seed": getattr(req, "seed", 0),
                     "logprobs": getattr(req, "logprobs", None) or 0}
+        sampling.update(_penalties_of(req))
         # checkpoint generation_config eos ids (possibly several, e.g.
         # llama-3) win over the tokenizer's probed eos token
         eos_ids = (entry.card or {}).get("eos_token_ids")
@@ -581,6 +649,7 @@ def build_app(manager: ModelManager,
     @app.post("/v1/completions")
     async def completions(req: CompletionRequest, raw: Request):
         entry = _entry_or_404(_model_of(req))
+        _check_penalties(entry, req)
         REQS.labels(entry.name, "completions").inc()
         if isinstance(req.prompt, list):
             token_ids = list(req.prompt)
@@ -886,6 +955,7 @@ def build_app(manager: ModelManager,
     @app.post("/v1/chat/completions")
     async def chat(req: ChatRequest, raw: Request):
         entry = _entry_or_404(_model_of(req))
+        _check_penalties(entry, req)
         REQS.labels(entry.name, "chat").inc()
         mm_extra = None
         mm = await _mm_prepare(entry, req)

@@ -590,3 +590,31 @@ def lora_delta_(y, x, bank, slots):
     lora_shrink(t, x, A_bank, slots, ranks)
     lora_expand_add(y, t, B_bank, slots, ranks, scales)
     return y
+
+
+# --------------------------------------------------------------------------
+# Per-request logit processors (csrc/logits_process.hip; the semantics are
+# written out at torch_ref.apply_logit_processors). engine/penalties.py owns
+# the bank and builds the per-step tensors.
+def penalty_fold(counts, slots, tokens, is_prompt):
+    """Add entries (slots[i], tokens[i], is_prompt[i]), int32 each, to the
+    [slots, V] int32 bank `counts` (word = prompt bit | output count << 1)."""
+    if counts.is_cuda:
+        hip().penalty_fold(counts, slots, tokens, is_prompt)
+        return counts
+    return torch_ref.penalty_fold(counts, slots, tokens, is_prompt)
+
+
+def apply_logit_processors(logits, counts, slots, params, bias=None,
+                           allow_fast: bool = True):
+    """Penalties, logit_bias and min_p in place on contiguous fp32 logits
+    [B, V]: bank `counts` (or None if no row has a slot), slots [B] int32
+    (-1 = none), params [B, 5] fp32 = (repetition, presence, frequency, min_p,
+    temperature), bias = (offsets [B + 1] int32, ids int32, vals fp32) or
+    None. Rows with neutral parameters stay bit-untouched."""
+    if logits.is_cuda:
+        hip().logits_process(logits, counts, slots, params,
+                             *(bias or (None, None, None)), allow_fast)
+        return logits
+    return torch_ref.apply_logit_processors(logits, counts, slots, params,
+                                            bias)

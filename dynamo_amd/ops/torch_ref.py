@@ -207,3 +207,63 @@ def lora_expand_add(y, t, B_bank, slots, ranks, scales):
         d = B_bank[s, :, :r].float() @ t[i, :r].float()
         y[i] = (y[i].float() + sc[s] * d).to(y.dtype)
     return y
+
+
+# --------------------------------------------------------------------------
+# Per-request logit processors: the contract of csrc/logits_process.hip.
+# The bank `counts` is int32 [slots, V]: bit 0 of a word says the token occurs
+# in the request's prompt, bits 1.. count its occurrences in the output.
+PENALTY_PROMPT_BIT = 1
+PENALTY_COUNT_ONE = 2
+
+
+def penalty_fold(counts, slots, tokens, is_prompt):
+    """Add entry i = (slots[i], tokens[i], is_prompt[i]) to the bank: set the
+    prompt bit or add one to the output count. Entries that name a slot or a
+    token outside the bank are skipped."""
+    S, V = counts.shape
+    for s, t, p in zip(slots.tolist(), tokens.tolist(), is_prompt.tolist()):
+        if 0 <= s < S and 0 <= t < V:
+            if p:
+                counts[s, t] |= PENALTY_PROMPT_BIT
+            else:
+                counts[s, t] += PENALTY_COUNT_ONE
+    return counts
+
+
+def apply_logit_processors(logits, counts, slots, params, bias=None):
+    """In place on fp32 logits [B, V], row b with params[b] = (repetition r,
+    presence, frequency, min_p, temperature T), bank row slots[b] (-1: none)
+    and bias = (offsets [B + 1], ids, vals) in CSR form or None, in this
+    order, all in fp32:
+      1. r != 1: l = l / r if l > 0 else l * r for every token in the prompt
+         or the output
+      2. l -= frequency * cnt + presence for every token with output count
+         cnt > 0
+      3. l[id] += val for the row's bias entries
+      4. min_p > 0 and T > 0: l = -inf where (l - max l) / T < ln(min_p)
+    A row with neutral parameters is not written."""
+    B, V = logits.shape
+    sl = slots.tolist()
+    off = bias[0].tolist() if bias is not None else None
+    for b in range(B):
+        rep, pres, freq, min_p, temp = params[b].unbind()
+        row = logits[b]
+        s = sl[b]
+        if (counts is not None and 0 <= s < counts.shape[0]
+                and (rep != 1 or pres != 0 or freq != 0)):
+            w = counts[s]
+            cnt = w >> 1
+            if rep != 1:
+                pen = torch.where(row > 0, row / rep, row * rep)
+                row.copy_(torch.where(w != 0, pen, row))
+            row.copy_(torch.where(
+                cnt > 0, row - (freq * cnt.float() + pres), row))
+        if off is not None and off[b + 1] > off[b]:
+            ids = bias[1][off[b]:off[b + 1]].long()
+            ok = (ids >= 0) & (ids < V)
+            row[ids[ok]] += bias[2][off[b]:off[b + 1]][ok]
+        if min_p > 0 and temp > 0:
+            drop = (row - row.max()) / temp < torch.log(min_p)
+            row.masked_fill_(drop, float("-inf"))
+    return logits

@@ -32,6 +32,11 @@ async def _one(client, url: str, rec: dict, results: list):
         "seed": rec.get("sampling", {}).get("seed", 0),
         "ignore_eos": rec.get("stop", {}).get("ignore_eos", False),
     }
+    # the logit processors, where the recorded request set them
+    for k in ("repetition_penalty", "presence_penalty", "frequency_penalty",
+              "min_p", "logit_bias"):
+        if rec.get("sampling", {}).get(k) is not None:
+            body[k] = rec["sampling"][k]
     t0 = time.monotonic()
     r = await client.post(url + "/v1/completions", json=body)
     dt = time.monotonic() - t0

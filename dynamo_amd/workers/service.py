@@ -10,7 +10,8 @@ Fulfills the worker contract the reference defines for its engine adapters
 
 Request payload (PreprocessedRequest parity,
 lib/llm/src/protocols/common/preprocessor.rs:243):
-  {request_id, token_ids, sampling_options{temperature, top_p, top_k, seed},
+  {request_id, token_ids, sampling_options{temperature, top_p, top_k, seed,
+   repetition_penalty, presence_penalty, frequency_penalty, min_p, logit_bias},
    stop_conditions{max_tokens, stop_token_ids, ignore_eos},
    routing{worker_instance_id?}, prefill_result?, annotations?}
 Response chunks (LLMEngineOutput parity, llm_backend.rs:163):
@@ -19,6 +20,7 @@ Response chunks (LLMEngineOutput parity, llm_backend.rs:163):
 from __future__ import annotations
 
 import asyncio
+import dataclasses
 import logging
 import time
 from typing import Any, AsyncIterator, Dict, Optional
@@ -46,6 +48,11 @@ def make_sampling(payload: dict) -> SamplingParams:
         seed=int(so.get("seed", 0)),
         embed=bool(so.get("embed", False)),
         logprobs=int(so.get("logprobs", 0)),
+        repetition_penalty=float(so.get("repetition_penalty", 1.0)),
+        presence_penalty=float(so.get("presence_penalty", 0.0)),
+        frequency_penalty=float(so.get("frequency_penalty", 0.0)),
+        min_p=float(so.get("min_p", 0.0)),
+        logit_bias=so.get("logit_bias") or {},
     )
 
 
@@ -328,9 +335,10 @@ class WorkerService:
         sp = make_sampling(payload)
         is_prefill_role = self.worker_type == "prefill"
         if is_prefill_role:
-            sp = SamplingParams(max_tokens=1, temperature=sp.temperature,
-                                top_p=sp.top_p, top_k=sp.top_k,
-                                seed=sp.seed, ignore_eos=True)
+            # the first token is sampled here: the logit processors stay
+            sp = dataclasses.replace(sp, max_tokens=1, ignore_eos=True,
+                                     stop_token_ids=[], embed=False,
+                                     logprobs=0)
 
         trace_event("handle_payload", request_id=req_id,
                     worker_id=self.instance_id, worker_type=self.worker_type,

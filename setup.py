@@ -27,6 +27,7 @@ hip_sources = [
         "attention_prefill.hip",
         "skinny_gemm.hip",
         "sampling.hip",
+        "logits_process.hip",
         "moe.hip",
         "lora.hip",
         "ipc.hip",
