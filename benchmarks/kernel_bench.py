@@ -273,6 +273,11 @@ def bench_skinny_gemm(M=16, sweep=False, mxfp4_sweep=False):
               f"n{cfg[2]} ({shipped}): {row}")
         t_bf16 = min(ts["lib"] if shipped == "library" or M > 16
                      else ts["nt"])
+        if name == "gateup" and M <= 16 and cfg[4]:
+            _bench_fused_glu(
+                f"{name:8s}[{M}x{K}x{N}] R={R} w{cfg[0]}u{cfg[1]}n{cfg[2]}",
+                "bf16_coalesced", cfg, y, lambda out, r, glu:
+                ops.hip().skinny_gemm(out, x, ws[r % R], *cfg, glu))
         _bench_fp8_gemm(name, x, ws, y, t_bf16, sweep)
         if name != "lm_head":       # not quantised by weight_dtype="mxfp4"
             _bench_mxfp4_gemm(name, x, ws, y, t_bf16, mxfp4_sweep)
@@ -307,6 +312,12 @@ def _bench_fp8_gemm(name, x, ws, y, t_bf16, sweep):
         print(f"gemm cold {name:8s}[{M}x{K}x{N}] R={R8} fp8 w{cfg[0]}u{cfg[1]}"
               f"n{cfg[2]}: {t*1e6:7.1f} us {wbytes/1e9/t/1e3:5.2f} TB/s "
               f"({t_bf16/t:4.2f}x the bf16 dispatch)")
+        if name == "gateup" and not sweep:
+            _bench_fused_glu(
+                f"{name:8s}[{M}x{K}x{N}] R={R8} fp8 w{cfg[0]}u{cfg[1]}"
+                f"n{cfg[2]}", "fp8", cfg, y, lambda out, r, glu, cfg=cfg:
+                ops.hip().fp8_skinny_gemm(out, x, qs[r % R8], scale, *cfg,
+                                          True, glu))
 
 
 def _bench_mxfp4_gemm(name, x, ws, y, t_bf16, sweep):
@@ -339,6 +350,48 @@ def _bench_mxfp4_gemm(name, x, ws, y, t_bf16, sweep):
               f"u{cfg[1]}n{cfg[2]}: {t*1e6:7.1f} us "
               f"{wbytes/1e9/t/1e3:5.2f} TB/s "
               f"({t_bf16/t:4.2f}x the bf16 dispatch)")
+        if name == "gateup" and not sweep:
+            _bench_fused_glu(
+                f"{name:8s}[{M}x{K}x{N}] R={R4} mxfp4 w{cfg[0]}u{cfg[1]}"
+                f"n{cfg[2]}", "mxfp4", cfg, y, lambda out, r, glu, cfg=cfg:
+                ops.hip().mxfp4_skinny_gemm(out, x, *qs[r % R4], *cfg, True,
+                                            glu))
+
+
+def _bench_fused_glu(label, fmt, cfg, y, gemm):
+    """The gate/up GEMM with the SwiGLU epilogue against the unfused GEMM
+    followed by silu_mul, both cache-cold the same way: gemm(out, r, glu)
+    launches the format's kernel on weight copy r into out."""
+    if not ops.glu_capable(fmt, cfg):
+        print(f"gemm cold {label}: no fused SwiGLU form")
+        return
+    M, N = y.shape
+    act = torch.empty(M, N // 2, dtype=y.dtype, device=y.device)
+    i = [0]
+
+    def fused():
+        i[0] += 1
+        gemm(act, i[0], True)
+
+    def two():
+        i[0] += 1
+        gemm(y, i[0], False)
+        ops.hip().silu_mul(act, y)
+
+    def plain():
+        i[0] += 1
+        gemm(y, i[0], False)
+
+    tf, t2, tp = ([], [], [])
+    for _ in range(3):
+        tf.append(timeit(fused, iters=24))
+        t2.append(timeit(two, iters=24))
+        tp.append(timeit(plain, iters=24))
+    ts = min(timeit(lambda: ops.hip().silu_mul(act, y), iters=24)
+             for _ in range(3))
+    print(f"gemm cold {label} +silu_mul: fused {min(tf)*1e6:7.1f} us | "
+          f"gemm, then silu_mul {min(t2)*1e6:7.1f} us (gemm {min(tp)*1e6:7.1f}"
+          f" + silu_mul alone, hot {ts*1e6:5.1f})")
 
 
 def bench_lora(T=16, R=64):

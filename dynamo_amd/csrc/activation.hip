@@ -21,12 +21,7 @@ __global__ void silu_mul_kernel(short* __restrict__ out,       // [T, I]
     short8 u = *reinterpret_cast<const short8*>(gu + t * 2 * I + I + i0);
     short8 o;
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
-      float gf = bf16_to_f32(g[i]);
-      float uf = bf16_to_f32(u[i]);
-      float s = gf / (1.f + __expf(-gf));
-      o[i] = f32_to_bf16(s * uf);
-    }
+    for (int i = 0; i < 8; i++) o[i] = silu_mul_bf16(g[i], u[i]);
     *reinterpret_cast<short8*>(out + t * I + i0) = o;
   }
 }

@@ -65,16 +65,18 @@ void logits_process(torch::Tensor logits, c10::optional<torch::Tensor> counts,
 // skinny_gemm.hip
 void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                  int64_t wpb, int64_t u, int64_t nt, bool nontemporal,
-                 bool coalesced);
+                 bool coalesced, bool glu);
 std::map<std::string, std::vector<std::tuple<int, int, int>>>
 skinny_gemm_configs();
+std::map<std::string, std::vector<std::tuple<int, int, int>>>
+skinny_gemm_glu_configs();
 void fp8_skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor wq,
                      torch::Tensor scale, int64_t wpb, int64_t u, int64_t nt,
-                     bool nontemporal);
+                     bool nontemporal, bool glu);
 void fp8_dequant(torch::Tensor out, torch::Tensor wq, torch::Tensor scale);
 void mxfp4_skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor q,
                        torch::Tensor scale, int64_t wpb, int64_t u,
-                       int64_t nt, bool nontemporal);
+                       int64_t nt, bool nontemporal, bool glu);
 int64_t mxfp4_gemm_max_m();
 void mxfp4_dequant(torch::Tensor out, torch::Tensor q, torch::Tensor scale);
 // lora.hip
@@ -155,16 +157,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias_off") = py::none(), py::arg("bias_ids") = py::none(),
         py::arg("bias_vals") = py::none(), py::arg("allow_fast") = true);
   // y = x @ w^T for 1 <= M <= 16 (decode); raises on anything the kernel
-  // does not handle - dispatch and fallback live in ops.linear
+  // does not handle - dispatch and fallback live in ops.linear. glu = true
+  // on any of the three GEMMs: w is a gate/up weight [2I, K], y is [M, I] =
+  // silu(gate) * up (row-coalesced formats, even NT; ops.linear_silu_mul)
   m.def("skinny_gemm", &skinny_gemm, py::arg("y"), py::arg("x"), py::arg("w"),
         py::arg("wpb") = 4, py::arg("u") = 4, py::arg("nt") = 2,
-        py::arg("nontemporal") = false, py::arg("coalesced") = false);
+        py::arg("nontemporal") = false, py::arg("coalesced") = false,
+        py::arg("glu") = false);
   // W8A16: y = (x @ bf16(wq)^T) * scale for 1 <= M <= 64, e4m3 weights with
   // one fp32 scale per row; raises on anything the kernel does not handle -
   // dispatch lives in ops.linear
   m.def("fp8_skinny_gemm", &fp8_skinny_gemm, py::arg("y"), py::arg("x"),
         py::arg("wq"), py::arg("scale"), py::arg("wpb") = 1, py::arg("u") = 1,
-        py::arg("nt") = 2, py::arg("nontemporal") = true);
+        py::arg("nt") = 2, py::arg("nontemporal") = true,
+        py::arg("glu") = false);
   m.def("fp8_dequant", &fp8_dequant, py::arg("out"), py::arg("wq"),
         py::arg("scale"));
   // W4A16: y = x @ W_eff^T for 1 <= M <= mxfp4_gemm_max_m(), OCP MXFP4
@@ -173,13 +179,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // ops.linear
   m.def("mxfp4_skinny_gemm", &mxfp4_skinny_gemm, py::arg("y"), py::arg("x"),
         py::arg("q"), py::arg("scale"), py::arg("wpb") = 1, py::arg("u") = 1,
-        py::arg("nt") = 2, py::arg("nontemporal") = true);
+        py::arg("nt") = 2, py::arg("nontemporal") = true,
+        py::arg("glu") = false);
   m.def("mxfp4_gemm_max_m", &mxfp4_gemm_max_m);
   m.def("mxfp4_dequant", &mxfp4_dequant, py::arg("out"), py::arg("q"),
         py::arg("scale"));
   // {"bf16_plain" | "bf16_coalesced" | "fp8" | "mxfp4": [(WPB, U, NT), ...]}:
   // what the GEMM bindings can launch
   m.def("skinny_gemm_configs", &skinny_gemm_configs);
+  // the same, restricted to the entries that take glu = true
+  m.def("skinny_gemm_glu_configs", &skinny_gemm_glu_configs);
   // batched LoRA: each row i takes the adapter in bank slot slots[i] (a
   // device tensor; < 0 = none), so one captured graph serves any adapter mix.
   // t[i, r] = x[i] . A_bank[s, r] and y[i] += scales[s] * t[i] @ B_bank[s]^T

@@ -44,6 +44,16 @@ DEVINL short f32_to_bf16(float f) {
   return (short)(rounded >> 16);
 }
 
+// SwiGLU on one bf16 (gate, up) pair: bf16(silu(gate) * up), fp32 inside.
+// The one place this arithmetic lives: silu_mul_kernel (activation.hip) and
+// the GLU epilogue of skinny_gemm_kernel must give equal bits.
+DEVINL short silu_mul_bf16(short gate, short up) {
+  float gf = bf16_to_f32(gate);
+  float uf = bf16_to_f32(up);
+  float s = gf / (1.f + __expf(-gf));
+  return f32_to_bf16(s * uf);
+}
+
 // ---- wave reductions ----------------------------------------------------
 DEVINL float wave_reduce_sum(float x) {
 #pragma unroll

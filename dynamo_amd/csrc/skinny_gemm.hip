@@ -12,6 +12,10 @@
 //                    uint8 [N,K/32] (e8m0), 1 <= M <= 16 MXFP4_GEMM_MAX_MT;
 //                    u counts 256-k steps.
 //   mxfp4_dequant:   out[N,K] = bf16(W_eff[N,K]).
+// `glu` selects the fused SwiGLU form of the three GEMMs: w is a gate/up
+// weight [2I, K] (gate rows first), y is [M, I] = silu(gate) * up with the
+// bits of silu_mul on the plain form's result. N % 32 == 0 and a table
+// entry skinny::glu_capable lists only.
 // `nontemporal` is the cache policy of the W loads. The launchers use the
 // current stream and neither allocate nor synchronise, so they can run inside
 // the captured decode graph.
@@ -29,17 +33,19 @@ struct GemmArgs {
   int M, N, K;
   int64_t wpb, u, nt;
   bool nontemporal;
+  bool glu;
 };
 
 // Everything the GEMM entry points require of their arguments but the W and
 // scale dtypes; max_m, min_k and k_per_step are the format's limits. w is
-// [N, K / w_pack]; scale is [N], or [N, K / 32] if block_scaled.
+// [N, K / w_pack]; scale is [N], or [N, K / 32] if block_scaled. y is [M, N],
+// or [M, N / 2] if glu.
 GemmArgs check_args(const char* name, int64_t max_m, int64_t min_k,
                     int64_t k_per_step, const torch::Tensor& y,
                     const torch::Tensor& x, const torch::Tensor& w,
                     const torch::Tensor* scale, int64_t wpb, int64_t u,
-                    int64_t nt, bool nontemporal, int64_t w_pack = 1,
-                    bool block_scaled = false) {
+                    int64_t nt, bool nontemporal, bool glu,
+                    int64_t w_pack = 1, bool block_scaled = false) {
   TORCH_CHECK(x.is_cuda() && w.is_cuda() && y.is_cuda() &&
                   (!scale || scale->is_cuda()),
               name, ": tensors must be on the GPU");
@@ -52,7 +58,8 @@ GemmArgs check_args(const char* name, int64_t max_m, int64_t min_k,
                   (!scale || scale->is_contiguous()),
               name, ": tensors must be contiguous");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(w.size(1) * w_pack == K && y.size(0) == M && y.size(1) == N &&
+  TORCH_CHECK(w.size(1) * w_pack == K && y.size(0) == M &&
+                  y.size(1) == (glu ? N / 2 : N) &&
                   (!scale || scale->size(0) == N) &&
                   (!block_scaled || scale->size(1) * 32 == K),
               name, ": shape mismatch");
@@ -60,6 +67,9 @@ GemmArgs check_args(const char* name, int64_t max_m, int64_t min_k,
               ", got ", M);
   TORCH_CHECK(N >= 16 && N % 16 == 0, name, ": needs N % 16 == 0, got ", N);
   TORCH_CHECK(N < (1 << 27), name, ": N too large");
+  TORCH_CHECK(!glu || (N % 32 == 0 && nt % 2 == 0), name,
+              ": the fused SwiGLU form needs N % 32 == 0 and an even NT, got "
+              "N = ", N, ", NT = ", nt);
   TORCH_CHECK(wpb > 0 && u > 0 && nt > 0, name, ": bad configuration");
   const int64_t kstep = wpb * k_per_step * u;
   TORCH_CHECK(K >= min_k && K < (1 << 30) && K % kstep == 0, name,
@@ -72,25 +82,36 @@ GemmArgs check_args(const char* name, int64_t max_m, int64_t min_k,
   return {(const short*)x.data_ptr(), w.data_ptr(),
           scale ? scale->data_ptr() : nullptr,
           (short*)y.data_ptr(), (int)M, (int)N, (int)K, wpb, u, nt,
-          nontemporal};
+          nontemporal, glu};
 }
 
 // Launches <F, WPB, U, NT> at ceil(M / 16) accumulator tiles, MT at the most.
-template <class F, int WPB, int U, int NT, int MT>
+// A GLU block owns NT / 2 of the N / 2 output column tiles: the same grid.
+template <class F, int WPB, int U, int NT, int MT, int GLU>
 void launch(const GemmArgs& a) {
   if constexpr (MT > 1) {
-    if (a.M <= (MT - 1) * 16) return launch<F, WPB, U, NT, MT - 1>(a);
+    if (a.M <= (MT - 1) * 16) return launch<F, WPB, U, NT, MT - 1, GLU>(a);
   }
   const int grid = (a.N + NT * 16 - 1) / (NT * 16);
   auto stream = at::cuda::getCurrentHIPStream();
   auto w = (const typename F::welem*)a.w;
   auto scale = (const typename F::scale_t*)a.scale;
   if (a.nontemporal)
-    skinny::skinny_gemm_kernel<F, WPB, U, NT, MT, 1>
+    skinny::skinny_gemm_kernel<F, WPB, U, NT, MT, 1, GLU>
         <<<grid, WPB * 64, 0, stream>>>(a.x, w, scale, a.y, a.M, a.N, a.K);
   else
-    skinny::skinny_gemm_kernel<F, WPB, U, NT, MT, 0>
+    skinny::skinny_gemm_kernel<F, WPB, U, NT, MT, 0, GLU>
         <<<grid, WPB * 64, 0, stream>>>(a.x, w, scale, a.y, a.M, a.N, a.K);
+}
+
+// The plain form, or the GLU one where the table entry has one.
+template <class F, int WPB, int U, int NT, int MT>
+void launch_form(const char* name, const GemmArgs& a) {
+  if (!a.glu) return launch<F, WPB, U, NT, MT, 0>(a);
+  if constexpr (skinny::glu_capable<F>(WPB, U, NT))
+    return launch<F, WPB, U, NT, MT, 1>(a);
+  TORCH_CHECK(false, name, ": no fused SwiGLU kernel for (WPB, U, NT) = (",
+              WPB, ", ", U, ", ", NT, ") of this format");
 }
 
 typedef std::vector<std::tuple<int, int, int>> ConfigList;
@@ -99,8 +120,10 @@ typedef std::vector<std::tuple<int, int, int>> ConfigList;
 // NAME_configs() is TABLE as a list.
 #define GEMM_CASE(WPB, U, NT)                                                \
   if (a.wpb == WPB && a.u == U && a.nt == NT)                                \
-    return launch<Format, WPB, U, NT, kMaxMt>(a);
+    return launch_form<Format, WPB, U, NT, kMaxMt>(name, a);
 #define GEMM_ENTRY(WPB, U, NT) {WPB, U, NT},
+#define GEMM_GLU_ENTRY(WPB, U, NT)                                           \
+  if (skinny::glu_capable<Format>(WPB, U, NT)) l.push_back({WPB, U, NT});
 #define GEMM_DISPATCH(NAME, F, MAX_MT, TABLE)                                \
   void NAME(const char* name, const GemmArgs& a) {                           \
     using Format = F;                                                        \
@@ -109,13 +132,20 @@ typedef std::vector<std::tuple<int, int, int>> ConfigList;
     TORCH_CHECK(false, name, ": no kernel for (WPB, U, NT) = (", a.wpb,      \
                 ", ", a.u, ", ", a.nt, ")");                                 \
   }                                                                          \
-  ConfigList NAME##_configs() { return {TABLE(GEMM_ENTRY)}; }
+  ConfigList NAME##_configs() { return {TABLE(GEMM_ENTRY)}; }              \
+  ConfigList NAME##_glu_configs() {                                          \
+    using Format = F;                                                        \
+    ConfigList l;                                                            \
+    TABLE(GEMM_GLU_ENTRY)                                                    \
+    return l;                                                                \
+  }
 GEMM_DISPATCH(launch_plain, skinny::Bf16Plain, 1, SKINNY_GEMM_CONFIGS)
 GEMM_DISPATCH(launch_coal, skinny::Bf16Coal, 1, SKINNY_GEMM_COAL_CONFIGS)
 GEMM_DISPATCH(launch_fp8, skinny::Fp8Coal, 4, FP8_GEMM_CONFIGS)
 GEMM_DISPATCH(launch_mxfp4, skinny::Mxfp4Coal, MXFP4_GEMM_MAX_MT,
               MXFP4_GEMM_CONFIGS)
 #undef GEMM_DISPATCH
+#undef GEMM_GLU_ENTRY
 #undef GEMM_ENTRY
 #undef GEMM_CASE
 
@@ -123,13 +153,13 @@ GEMM_DISPATCH(launch_mxfp4, skinny::Mxfp4Coal, MXFP4_GEMM_MAX_MT,
 
 void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                  int64_t wpb, int64_t u, int64_t nt, bool nontemporal,
-                 bool coalesced) {
+                 bool coalesced, bool glu) {
   const char* name = "skinny_gemm";
   TORCH_CHECK(w.dtype() == torch::kBFloat16, name, ": w must be bf16");
   const GemmArgs a = check_args(
       name, 16, 2048,
       coalesced ? skinny::Bf16Coal::KSTEP : skinny::Bf16Plain::KSTEP, y, x, w,
-      nullptr, wpb, u, nt, nontemporal);
+      nullptr, wpb, u, nt, nontemporal, glu);
   if (coalesced) launch_coal(name, a);
   else launch_plain(name, a);
   HIP_CHECK_KERNEL();
@@ -137,25 +167,25 @@ void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
 
 void fp8_skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor wq,
                      torch::Tensor scale, int64_t wpb, int64_t u, int64_t nt,
-                     bool nontemporal) {
+                     bool nontemporal, bool glu) {
   const char* name = "fp8_skinny_gemm";
   TORCH_CHECK(wq.dtype() == at::kFloat8_e4m3fn, name,
               ": wq must be float8_e4m3fn");
   TORCH_CHECK(scale.dtype() == torch::kFloat32, name, ": scale must be fp32");
   launch_fp8(name, check_args(name, 64, 128, skinny::Fp8Coal::KSTEP, y, x, wq,
-                              &scale, wpb, u, nt, nontemporal));
+                              &scale, wpb, u, nt, nontemporal, glu));
   HIP_CHECK_KERNEL();
 }
 
 void mxfp4_skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor q,
                        torch::Tensor scale, int64_t wpb, int64_t u,
-                       int64_t nt, bool nontemporal) {
+                       int64_t nt, bool nontemporal, bool glu) {
   const char* name = "mxfp4_skinny_gemm";
   TORCH_CHECK(q.dtype() == torch::kUInt8 && scale.dtype() == torch::kUInt8,
               name, ": q and scale must be uint8");
   launch_mxfp4(name, check_args(name, 16 * MXFP4_GEMM_MAX_MT, 256,
                                 skinny::Mxfp4Coal::KSTEP, y, x, q, &scale,
-                                wpb, u, nt, nontemporal,
+                                wpb, u, nt, nontemporal, glu,
                                 skinny::Mxfp4Coal::WPACK, true));
   HIP_CHECK_KERNEL();
 }
@@ -167,6 +197,14 @@ std::map<std::string, ConfigList> skinny_gemm_configs() {
           {"bf16_coalesced", launch_coal_configs()},
           {"fp8", launch_fp8_configs()},
           {"mxfp4", launch_mxfp4_configs()}};
+}
+
+// The entries of those tables that have a fused SwiGLU form.
+std::map<std::string, ConfigList> skinny_gemm_glu_configs() {
+  return {{"bf16_plain", launch_plain_glu_configs()},
+          {"bf16_coalesced", launch_coal_glu_configs()},
+          {"fp8", launch_fp8_glu_configs()},
+          {"mxfp4", launch_mxfp4_glu_configs()}};
 }
 
 int64_t mxfp4_gemm_max_m() { return 16 * MXFP4_GEMM_MAX_MT; }

@@ -76,6 +76,7 @@
 #pragma once
 
 #include "common.h"
+#include <type_traits>
 
 namespace skinny {
 
@@ -238,19 +239,32 @@ struct Mxfp4Coal {
 // read row 0 and tile columns >= N read column N-1 (clamped addresses);
 // neither is stored. scale is read only if F::SCALED ([N]) or
 // F::BLOCK_SCALED ([N, K / 32]).
-template <class F, int WPB, int U, int NT, int MT, int NTL>
+//
+// GLU = 1 fuses the SwiGLU activation of a gate/up projection: w is [2I, K],
+// gate rows first and up rows second, N = 2I, and y is [M, I] =
+// silu(gate) * up. NT must be even. A block owns NT/2 column tiles of y; its
+// weight tiles 0 .. NT/2-1 are their gate rows and NT/2 .. NT-1 the matching
+// up rows at + I, so the lane that holds gate column j in acc[t] holds up
+// column I + j in acc[t + NT/2]. The K loop and the reduction are those of
+// GLU = 0; the epilogue rounds both sums to bf16 as the plain one does and
+// applies silu_mul_bf16, so y has the bits of silu_mul_kernel on the plain
+// kernel's result. Requires I % 16 == 0.
+template <class F, int WPB, int U, int NT, int MT, int NTL, int GLU = 0>
 __global__ __launch_bounds__(WPB * 64) void skinny_gemm_kernel(
     const short* __restrict__ x,               // [M, K] bf16 row-major
     const typename F::welem* __restrict__ w,   // [N, K] row-major
     const typename F::scale_t* __restrict__ scale,
     short* __restrict__ y,                     // [M, N] bf16 row-major
     int M, int N, int K) {
+  static_assert(!GLU || NT % 2 == 0, "GLU pairs gate and up tiles");
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;       // 0..WPB-1 = k-slice
   const int lr = lane & 15;
   const int lg = lane >> 4;
-  const int n0 = (blockIdx.x * NT) * 16;  // first col of this block's tiles
-  if (n0 >= N) return;
+  constexpr int NTO = GLU ? NT / 2 : NT;  // column tiles of y per block
+  const int NO = GLU ? N / 2 : N;         // columns of y
+  const int n0 = (blockIdx.x * NTO) * 16; // first col of this block's tiles
+  if (n0 >= NO) return;
 
   const int kw = K / WPB;                 // K per wave
   const int k0 = wid * kw;
@@ -267,16 +281,20 @@ __global__ __launch_bounds__(WPB * 64) void skinny_gemm_kernel(
   for (int t = 0; t < NT; t++)
 #pragma unroll
     for (int h = 0; h < F::LOADS; h++) {
-      const int col = n0 + t * 16 + F::w_row(lane, h);
-      wp[t][h] = w + (size_t)(col < N ? col : N - 1) * (K / F::WPACK) +
+      int col = n0 + (t % NTO) * 16 + F::w_row(lane, h);
+      col = col < NO ? col : NO - 1;
+      if (GLU && t >= NTO) col += NO;   // the up row of that column
+      wp[t][h] = w + (size_t)col * (K / F::WPACK) +
                  k0 / F::WPACK + F::w_k(lane);
     }
   const typename F::scale_t* sp[NT];
   if constexpr (F::BLOCK_SCALED) {
 #pragma unroll
     for (int t = 0; t < NT; t++) {
-      const int col = n0 + t * 16 + lr;
-      sp[t] = scale + ((size_t)(col < N ? col : N - 1) * K + k0) / 32;
+      int col = n0 + (t % NTO) * 16 + lr;
+      col = col < NO ? col : NO - 1;
+      if (GLU && t >= NTO) col += NO;
+      sp[t] = scale + ((size_t)col * K + k0) / 32;
     }
   }
 
@@ -382,6 +400,28 @@ __global__ __launch_bounds__(WPB * 64) void skinny_gemm_kernel(
     if (wid > 0) return;
   }
   // C layout: lane holds y[16 m + lg*4 + i][tilecol + lr], i = 0..3.
+  if constexpr (GLU) {
+#pragma unroll
+    for (int t = 0; t < NTO; t++) {
+      const int col = n0 + t * 16 + lr;
+      if (col >= NO) continue;
+      float sg = 1.f, su = 1.f;
+      if constexpr (F::SCALED) { sg = scale[col]; su = scale[col + NO]; }
+#pragma unroll
+      for (int m = 0; m < MT; m++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int row = m * 16 + lg * 4 + i;
+          if (row < M) {
+            float g = acc[t][m][i], u = acc[t + NTO][m][i];
+            if constexpr (F::SCALED) { g *= sg; u *= su; }
+            y[(size_t)row * NO + col] =
+                silu_mul_bf16(f32_to_bf16(g), f32_to_bf16(u));
+          }
+        }
+    }
+    return;
+  }
 #pragma unroll
   for (int t = 0; t < NT; t++) {
     const int col = n0 + t * 16 + lr;
@@ -473,5 +513,15 @@ __global__ __launch_bounds__(256) void mxfp4_dequant_kernel(
   X(1, 1, 1) X(1, 1, 2) X(1, 2, 2) X(2, 1, 2) X(2, 1, 4) X(4, 1, 2)          \
   X(4, 1, 4) X(4, 1, 8) X(8, 1, 2) X(8, 1, 4) X(2, 1, 8)
 #define MXFP4_GEMM_MAX_MT 2
+
+// Whether point (WPB, U, NT) of format F's table has a GLU = 1 form: the
+// row-coalesced formats at even NT, but for Bf16Coal (8, 1, 4), the one point
+// whose GLU form would run fewer waves per SIMD than its plain twin (136
+// against 99 VGPRs, 3 against 4 waves). ops/__init__.py keeps a copy.
+template <class F>
+constexpr bool glu_capable(int wpb, int u, int nt) {
+  if (std::is_same<F, Bf16Plain>::value || nt % 2) return false;
+  return !(std::is_same<F, Bf16Coal>::value && wpb == 8 && u == 1 && nt == 4);
+}
 
 }  // namespace skinny

@@ -36,6 +36,10 @@ ENV_VARS = {
     "DYNAMO_SKINNY_GEMM":
         "0 = every decode weight GEMM on hipBLASLt (default: the in-tree "
         "skinny-M kernel on the shapes in ops.SKINNY_GEMM_SHAPES)",
+    "DYNAMO_FUSED_GLU":
+        "0 = gate/up GEMM and silu_mul as two kernels (default: the in-tree "
+        "GEMM applies SwiGLU in its epilogue where ops.fused_glu_config "
+        "allows; equal bits either way)",
     "DYNAMO_MAX_LORAS":
         "default of the worker's --max-loras: adapter-bank slots for "
         "per-request LoRA (default 0 = engine-level activation only)",

@@ -280,11 +280,15 @@ class SwiGLUMLP(torch.nn.Module):
 
     def forward(self, x, meta: Optional[AttnMetadata] = None):
         batched = meta is not None and meta.lora_slots is not None
-        gu = linear_lora(x, self.w_gate_up, self.lora, "gate_up")
-        if batched:
-            lora_bank_delta_(gu, x, self.lora_bank["gate_up"], meta)
-        # silu_mul expects [., 2I] with gate then up
-        act = ops.silu_mul(gu)
+        if not batched and not (self.lora and "gate_up" in self.lora):
+            # no LoRA delta lands on gate/up: the GEMM applies the activation
+            act = ops.linear_silu_mul(x, self.w_gate_up)
+        else:
+            gu = linear_lora(x, self.w_gate_up, self.lora, "gate_up")
+            if batched:
+                lora_bank_delta_(gu, x, self.lora_bank["gate_up"], meta)
+            # silu_mul expects [., 2I] with gate then up
+            act = ops.silu_mul(gu)
         down = linear_lora(act, self.w_down, self.lora, "down")
         if batched:
             lora_bank_delta_(down, act, self.lora_bank["down"], meta)

@@ -159,11 +159,13 @@ def _quant_linear_path(x, w, dequant_k, gemm_config):
     return "dequant", None
 
 
-def _linear_quant(x, w, path, cfg, gemm: str, dequant: str):
-    """linear(x, w) on `path`; gemm and dequant name the format's bindings."""
+def _linear_quant(x, w, path, cfg, gemm: str, dequant: str, glu=False):
+    """linear(x, w) on `path`; gemm and dequant name the format's bindings.
+    glu (kernel path only): the fused SwiGLU form, y = [M, N / 2]."""
     if path == "kernel":
-        y = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
-        getattr(hip(), gemm)(y, x, w.q, w.scale, *cfg, True)
+        y = torch.empty(x.shape[0], w.shape[0] // 2 if glu else w.shape[0],
+                        dtype=x.dtype, device=x.device)
+        getattr(hip(), gemm)(y, x, w.q, w.scale, *cfg, True, glu)
         return y
     if path == "dequant":
         w_eff = fp8_weights.scratch_view(w)
@@ -261,6 +263,85 @@ def linear(x: torch.Tensor, w) -> torch.Tensor:
         return torch.nn.functional.linear(x, w)
     y = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
     hip().skinny_gemm(y, x, w, *cfg)
+    return y
+
+
+# --------------------------------------------------------------------------
+# Fused SwiGLU: the in-tree GEMM's GLU epilogue (csrc/skinny_gemm_impl.h)
+# computes silu(gate) * up from the accumulators, with the bits of silu_mul on
+# the plain kernel's result, and saves the silu_mul launch and the read-back
+# of the [M, 2I] intermediate.
+# The formats whose dispatch takes it. As with SKINNY_GEMM_SHAPES, a format is
+# listed only if its fused kernel beat the two kernels in situ in both of two
+# paired traces and end to end, with the parent's outputs (profiles/README.md,
+# "SwiGLU in the gate/up GEMM's epilogue").
+FUSED_GLU_FORMATS: tuple = ("bf16_coalesced", "fp8", "mxfp4")
+
+_fused_glu_override: "bool | None" = None
+
+
+def set_fused_glu(on: "bool | None") -> None:
+    """In-process override of DYNAMO_FUSED_GLU (None = follow the env)."""
+    global _fused_glu_override
+    _fused_glu_override = on
+
+
+def fused_glu_enabled() -> bool:
+    if _fused_glu_override is not None:
+        return _fused_glu_override
+    from dynamo_amd import envs
+    return envs.get("DYNAMO_FUSED_GLU", True, bool)
+
+
+def glu_capable(fmt: str, cfg) -> bool:
+    """Whether point (WPB, U, NT, ...) of table `fmt` ("bf16_coalesced" |
+    "fp8" | "mxfp4" | "bf16_plain") has a GLU instantiation; a copy of the
+    header's skinny::glu_capable, checked against
+    hip().skinny_gemm_glu_configs() by the tests. A block pairs NT / 2 gate
+    tiles with NT / 2 up tiles, so NT is even; the GLU form of bf16 (8, 1, 4)
+    would run 3 waves/SIMD where its plain twin runs 4 and is not built."""
+    if fmt == "bf16_plain" or cfg[2] % 2:
+        return False
+    return not (fmt == "bf16_coalesced" and tuple(cfg[:3]) == (8, 1, 4))
+
+
+def fused_glu_config(x: torch.Tensor, w):
+    """(binding name, configuration) if linear_silu_mul(x, w) runs on the
+    fused kernel, else None: linear(x, w) would take the in-tree kernel, its
+    configuration has a GLU form, its format is in FUSED_GLU_FORMATS and
+    I = N / 2 is a multiple of 16."""
+    if not fused_glu_enabled() or w.shape[0] % 32:
+        return None
+    if isinstance(w, Fp8Weight):
+        path, cfg = fp8_linear_path(x, w)
+        hit = ("fp8_skinny_gemm", "fp8", cfg) if path == "kernel" else None
+    elif isinstance(w, Mxfp4Weight):
+        path, cfg = mxfp4_linear_path(x, w)
+        hit = (("mxfp4_skinny_gemm", "mxfp4", cfg) if path == "kernel"
+               else None)
+    else:
+        cfg = skinny_gemm_config(x, w)
+        hit = None if cfg is None else (
+            "skinny_gemm", "bf16_coalesced" if cfg[4] else "bf16_plain", cfg)
+    if (hit is None or hit[1] not in FUSED_GLU_FORMATS
+            or not glu_capable(hit[1], hit[2])):
+        return None
+    return hit[0], hit[2]
+
+
+def linear_silu_mul(x: torch.Tensor, w_gate_up) -> torch.Tensor:
+    """silu_mul(linear(x, w_gate_up)) for a gate/up weight [2I, K], gate rows
+    first: one kernel where fused_glu_config allows it, else the two calls.
+    Equal bits either way."""
+    hit = fused_glu_config(x, w_gate_up)
+    if hit is None:
+        return silu_mul(linear(x, w_gate_up))
+    gemm, cfg = hit
+    if gemm != "skinny_gemm":
+        return _linear_quant(x, w_gate_up, "kernel", cfg, gemm, None, True)
+    y = torch.empty(x.shape[0], w_gate_up.shape[0] // 2, dtype=x.dtype,
+                    device=x.device)
+    hip().skinny_gemm(y, x, w_gate_up, *cfg, True)
     return y
 
 
