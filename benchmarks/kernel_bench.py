@@ -110,6 +110,21 @@ def bench_sampling(B=16, V=128256):
     logits = torch.randn(B, V, device="cuda")
     t = timeit(lambda: ops.greedy_sample(logits))
     print(f"greedy       [B{B} V{V}]: {t*1e6:8.1f} us")
+    # the filtered sampler with every row on the same filter, on N(0, 1)
+    # logits and on the nearly flat rows of the benchmark model (sigma 0.01);
+    # min of three, alternated, like every comparison in this file
+    inv_t = torch.ones(B, device="cuda")
+    modes = (("k only", 50, 1.0), ("p only", 0, 0.9), ("k and p", 50, 0.9))
+    for name, rows in (("randn", logits), ("flat", logits * 0.01)):
+        ts = {m[0]: [] for m in modes}
+        for _ in range(3):
+            for mode, k, p in modes:
+                tk = torch.full((B,), k, dtype=torch.int32, device="cuda")
+                tp = torch.full((B,), p, dtype=torch.float32, device="cuda")
+                ts[mode].append(timeit(
+                    lambda: ops.topkp_sample(rows, inv_t, tk, tp, 1234)))
+        row = " | ".join(f"{m} {min(v)*1e6:7.1f} us" for m, v in ts.items())
+        print(f"topkp_sample [B{B} V{V}] {name:5s}: {row}")
 
 
 def timeit_graph(fn, n=100, reps=20):

@@ -5,8 +5,9 @@
 //   argmax(logits/T + G_i), G_i = -log(-log(U_i)) with a counter-based
 //   in-kernel hash RNG (deterministic given seed; no host noise tensor).
 // Both are single-pass, vectorized, one workgroup per sequence.
-// top-k / top-p: one fused kernel, per-row thresholds by bisection, then the
-//   same Gumbel argmax over the surviving set (topkp_sample_kernel below).
+// top-k / top-p: one fused kernel, exact per-row thresholds by a search on
+//   the logit's bit pattern (top-k, then the nucleus of the survivors), then
+//   the same Gumbel argmax over the surviving set (topkp_sample_kernel below).
 //
 // Capability parity: the reference delegates sampling to its engines; this
 // is the native path. Penalties, logit_bias and min_p edit the logits before
@@ -118,23 +119,151 @@ __global__ __launch_bounds__(kBlock) void sample_kernel(
   }
 }
 
+// Order-preserving key of an fp32: a < b as floats iff key(a) < key(b) as
+// unsigned integers (-0 is folded into +0; NaNs land beyond the infinities).
+DEVINL uint32_t float_key(float x) {
+  uint32_t u = __float_as_uint(x);
+  if (u == 0x80000000u) u = 0;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// f(row[v], v) once for every v in [0, V) over the threads of the block,
+// each thread in the same order on every call: 16-byte loads, kScanUnroll in
+// flight per thread, with the scalar head and tail of sample_kernel<, true>
+// (valid for any V and any row alignment).
+template <class F>
+DEVINL void scan_row(const float* __restrict__ row, int V, F&& f) {
+  const int mis = (int)((reinterpret_cast<uintptr_t>(row) >> 2) & 3);
+  const int head = min(V, (4 - mis) & 3);
+  const int n4 = (V - head) / 4;
+  const float4v* row4 = reinterpret_cast<const float4v*>(row + head);
+  for (int i0 = 0; i0 < n4; i0 += kScanUnroll * kBlock) {
+    float4v r[kScanUnroll];
+#pragma unroll
+    for (int u = 0; u < kScanUnroll; u++) {
+      const int i = i0 + u * kBlock + threadIdx.x;
+      if (i < n4) r[u] = row4[i];
+    }
+#pragma unroll
+    for (int u = 0; u < kScanUnroll; u++) {
+      const int i = i0 + u * kBlock + threadIdx.x;
+      if (i < n4) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) f(r[u][e], head + i * 4 + e);
+      }
+    }
+  }
+  if ((int)threadIdx.x < head) f(row[threadIdx.x], (int)threadIdx.x);
+  const int v = head + n4 * 4 + threadIdx.x;
+  if (v < V) f(row[v], v);
+}
+
+constexpr int kCand = 8;  // thresholds tried per pass: 3 bits of the key
+
+// The smallest key t in [lo, hi] with stat(t) <= bound, where
+//   stat(t) = sum over { v : key(row[v]) > t } of w_v,
+// w_v = 1 (MASS false: a count) or __expf(row[v] - m) (MASS true: a mass,
+// and bound = top_p * stat(lo), taken from the first pass). Within a pass
+// stat does not grow with t, in fp32 too: the candidates add subsets of the
+// same terms in the same order. Across passes `base` is an earlier pass's
+// sum, so two passes can differ by fp32 rounding (~1e-7 of the mass). The
+// row is taken to hold no NaN (fmaxf skips one, so its key lies above hi
+// and neither search counts it; the final scan never draws it), and counts
+// are summed in fp32, exact for V < 2^24. hi is taken to meet the bound
+// without being tried, so the result never exceeds it. Each pass tries kCand keys that cut [lo, hi] into equal
+// parts, so 11 passes settle all 32 bits; elements at or below lo no longer
+// count and the ones above hi are carried in `base`, so once the range has
+// narrowed to a few exponents most waves skip most of the row. A count that
+// hits k exactly ends the search: that set is the top k.
+// `red` is kCand * kWaves floats of LDS. Every thread returns the same key.
+template <bool MASS>
+DEVINL uint32_t search_threshold(const float* __restrict__ row, int V, float m,
+                                 uint32_t lo, uint32_t hi, float bound,
+                                 float top_p, float* red) {
+  constexpr int kWaves = kBlock / WAVE_SIZE;
+  float base = 0.f;  // stat(hi)
+  bool first = true;
+  while (lo < hi) {
+    const uint32_t step = (hi - lo) / kCand + 1;
+    uint32_t c[kCand];
+#pragma unroll
+    for (int j = 0; j < kCand; j++)
+      c[j] = (uint32_t)min((uint64_t)lo + (uint64_t)j * step, (uint64_t)hi);
+    float acc[kCand];
+#pragma unroll
+    for (int j = 0; j < kCand; j++) acc[j] = 0.f;
+    scan_row(row, V, [&](float x, int) {
+      const uint32_t key = float_key(x);
+      if (key > lo && key <= hi) {
+        const float w = MASS ? __expf(x - m) : 1.f;
+#pragma unroll
+        for (int j = 0; j < kCand; j++) acc[j] += key > c[j] ? w : 0.f;
+      }
+    });
+#pragma unroll
+    for (int j = 0; j < kCand; j++) acc[j] = wave_reduce_sum(acc[j]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+      for (int j = 0; j < kCand; j++)
+        red[j * kWaves + threadIdx.x / WAVE_SIZE] = acc[j];
+    }
+    __syncthreads();
+    float stat[kCand];
+#pragma unroll
+    for (int j = 0; j < kCand; j++) {
+      float s = red[j * kWaves];
+      for (int w = 1; w < kWaves; w++) s += red[j * kWaves + w];
+      stat[j] = base + s;
+    }
+    __syncthreads();
+    if (MASS && first) bound = top_p * stat[0];
+    first = false;
+    // the candidates below hi, in order, up to the first that meets the
+    // bound: it becomes hi, the last one that misses it becomes lo - 1
+    uint32_t new_lo = lo, new_hi = hi;
+    bool done = false, exact = false;
+#pragma unroll
+    for (int j = 0; j < kCand; j++) {
+      if (done || c[j] >= hi) {
+        done = true;
+      } else if (stat[j] <= bound) {
+        new_hi = c[j];
+        base = stat[j];
+        done = true;
+      } else {
+        new_lo = c[j] + 1;
+        exact = !MASS && stat[j] == bound + 1.f;
+      }
+    }
+    lo = new_lo;
+    hi = exact ? new_lo : new_hi;
+  }
+  return lo;
+}
+
 // Fused top-k / top-p (nucleus) sampling: one block per row, no sort.
 //
-// The k-th-largest-prob threshold (top-k) and the nucleus mass threshold
-// (top-p) are found by a FUSED bisection on the probability scale: each
-// iteration makes one pass over the vocab computing count(p_i >= t_k) and
-// mass(p_i >= t_p) for the two candidate thresholds, 24 iterations
-// (resolution 6e-8 on [0,1] — tokens below that probability are sampling
-// noise). The final pass Gumbel-argmaxes logits/T over the surviving set,
-// which samples the renormalized filtered distribution exactly. Nucleus
-// semantics match the torch reference in engine/sampling.py: the keep-set
-// is defined on the T=1 softmax; temperature only shapes sampling inside
-// the set. Single launch, no host sync, hipGraph-capturable.
+// The keep set is torch_ref.topkp_keep_mask, exactly: top-k first, every
+// entry >= the k-th largest logit (a tie at the boundary is kept whole);
+// then the nucleus of the softmax over those survivors, a token being kept
+// iff the mass of the tokens strictly above it is <= top_p times the
+// survivors' mass. Both are thresholds on the logit, found by a search on
+// its order-preserving bit pattern (search_threshold), so they are exact
+// values of the row whatever its scale, and the top-k one needs no
+// exponential. A row runs only the searches its parameters switch on. The
+// threshold never exceeds the row maximum: the argmax survives any top_p
+// and -1 is never written for a row with a finite entry. The final pass is
+// gumbel_sample's scan (sample_consider) over the surviving set, which
+// samples the renormalized filtered distribution exactly and equals
+// gumbel_sample on the -inf masked row token for token. The keep set is
+// defined on the T=1 softmax, as in engine/sampling.py::_filter_topk_topp;
+// temperature only shapes sampling inside the set. Single launch, no host
+// sync, hipGraph-capturable.
 __global__ __launch_bounds__(kBlock) void topkp_sample_kernel(
     int32_t* __restrict__ out,          // [B]
     const float* __restrict__ logits,   // [B, V]
     const float* __restrict__ inv_temp, // [B]
-    const int32_t* __restrict__ top_k,  // [B] (<=0: off)
+    const int32_t* __restrict__ top_k,  // [B] (<=0 or >=V: off)
     const float* __restrict__ top_p,    // [B] (>=1: off)
     uint64_t seed,
     const uint64_t* __restrict__ row_seeds,  // [B] or null
@@ -147,80 +276,44 @@ __global__ __launch_bounds__(kBlock) void topkp_sample_kernel(
   const bool use_k = (k > 0 && k < V);
   const bool use_p = (p < 1.0f);
   constexpr int kWaves = kBlock / WAVE_SIZE;
-  __shared__ float red[kWaves];
-  __shared__ float red2[kWaves];
-  __shared__ float bcast[2];
+  __shared__ float red[kCand * kWaves];
+  __shared__ float bcast;
 
-  // pass 1: row max (softmax stability)
-  float m = -1e38f;
-  for (int v = threadIdx.x; v < V; v += kBlock) m = fmaxf(m, row[v]);
-  m = wave_reduce_max(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x / WAVE_SIZE] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; w++) m = fmaxf(m, red[w]);
-    bcast[0] = m;
-  }
-  __syncthreads();
-  m = bcast[0];
-
-  // pass 2: partition sum Z
-  float z = 0.f;
-  for (int v = threadIdx.x; v < V; v += kBlock) z += __expf(row[v] - m);
-  z = wave_reduce_sum(z);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x / WAVE_SIZE] = z;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; w++) z += red[w];
-    bcast[0] = z;
-  }
-  __syncthreads();
-  const float inv_z = 1.f / bcast[0];
-
-  // fused bisection: t_k (count >= k) and t_p (mass >= p), both on [0,1]
-  float lo_k = 0.f, hi_k = 1.f, lo_p = 0.f, hi_p = 1.f;
+  uint32_t thr = 0;  // keep { v : key(row[v]) >= thr }
   if (use_k || use_p) {
-    for (int it = 0; it < 24; it++) {
-      const float mid_k = 0.5f * (lo_k + hi_k);
-      const float mid_p = 0.5f * (lo_p + hi_p);
-      float cnt = 0.f, mass = 0.f;
-      for (int v = threadIdx.x; v < V; v += kBlock) {
-        const float pv = __expf(row[v] - m) * inv_z;
-        if (use_k && pv >= mid_k) cnt += 1.f;
-        if (use_p && pv >= mid_p) mass += pv;
-      }
-      cnt = wave_reduce_sum(cnt);
-      mass = wave_reduce_sum(mass);
-      const int wid = threadIdx.x / WAVE_SIZE;
-      if ((threadIdx.x & 63) == 0) { red[wid] = cnt; red2[wid] = mass; }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        for (int w = 1; w < kWaves; w++) { cnt += red[w]; mass += red2[w]; }
-        bcast[0] = cnt;
-        bcast[1] = mass;
-      }
-      __syncthreads();
-      cnt = bcast[0];
-      mass = bcast[1];
-      if (use_k) { if (cnt >= (float)k) lo_k = mid_k; else hi_k = mid_k; }
-      if (use_p) { if (mass >= p) lo_p = mid_p; else hi_p = mid_p; }
-      __syncthreads();
+    // row max: the top of both searches, and the softmax shift
+    float m = -1e38f;
+    scan_row(row, V, [&](float x, int) { m = fmaxf(m, x); });
+    m = wave_reduce_max(m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x / WAVE_SIZE] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int w = 1; w < kWaves; w++) m = fmaxf(m, red[w]);
+      bcast = m;
+    }
+    __syncthreads();
+    m = bcast;
+    __syncthreads();
+    const uint32_t top = float_key(m);
+    // the k-th largest key: the smallest t with count(key > t) <= k - 1
+    if (use_k)
+      thr = search_threshold<false>(row, V, m, 0, top, (float)(k - 1), 0.f,
+                                    red);
+    // the nucleus over { key >= thr }: starting one below thr makes the
+    // first pass's stat(lo) the survivors' mass
+    if (use_p) {
+      const uint32_t lo = thr > 0 ? thr - 1 : 0;
+      thr = max(thr, search_threshold<true>(row, V, m, lo, top, 0.f, p, red));
     }
   }
-  const float thr = fmaxf(use_k ? lo_k : 0.f, use_p ? lo_p : 0.f);
 
-  // final pass: Gumbel-argmax of logits/T over {p_i >= thr}
+  // final pass: Gumbel-argmax of logits/T over the surviving set
   const float it_ = inv_temp[b];
   float best = -1e38f;
   int besti = -1;
-  for (int v = threadIdx.x; v < V; v += kBlock) {
-    const float pv = __expf(row[v] - m) * inv_z;
-    if (pv < thr) continue;
-    const uint64_t h = hash_u64(rs ^ (uint64_t)v);
-    const float u = (float)((h >> 11) + 1) * 4.8828125e-4f * 2.2737367544323206e-13f;
-    const float x = row[v] * it_ + -__logf(-__logf(u));
-    if (x > best || (x == best && v < besti)) { best = x; besti = v; }
-  }
+  scan_row(row, V, [&](float x, int v) {
+    if (float_key(x) >= thr) sample_consider<true>(x, v, it_, rs, best, besti);
+  });
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const float ob = __shfl_xor(best, off, WAVE_SIZE);

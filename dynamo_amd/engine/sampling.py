@@ -1,6 +1,9 @@
 """Batch sampling: greedy (native HIP argmax) and temperature sampling via
-the native Gumbel-max kernel; top-k/top-p apply a torch-side logit filter
-first (filtered Gumbel-max samples the renormalized distribution exactly)."""
+the native Gumbel-max kernel; top-k/top-p go through the fused HIP kernel on
+the GPU and through a torch-side logit filter on the CPU. The two keep the
+same set except where equal logits straddle the nucleus boundary (see
+_filter_topk_topp); filtered Gumbel-max samples the renormalized
+distribution exactly."""
 from __future__ import annotations
 
 from typing import List
@@ -12,6 +15,14 @@ from .scheduler import Request
 
 
 def _filter_topk_topp(logits: torch.Tensor, top_k: int, top_p: float):
+    """top-k first (ties at the boundary all kept), then the nucleus of the
+    softmax over the survivors. The HIP topkp_sample kernel and its float64
+    reference, ops.torch_ref.topkp_keep_mask, keep the same set wherever no
+    run of equal logits straddles the nucleus boundary: the sort here splits
+    such a run by its own order, while they keep or drop it whole. The
+    cumulative sum here runs in the dtype of `logits` (fp32 in the engine),
+    so a top_p within fp32 rounding of a cumulative mass can also fall on
+    the other side."""
     if top_k > 0 and top_k < logits.shape[-1]:
         kth = torch.topk(logits, top_k, dim=-1).values[..., -1:]
         logits = logits.masked_fill(logits < kth, float("-inf"))
@@ -95,7 +106,9 @@ def sample_tokens(logits: torch.Tensor, reqs: List[Request],
     has_filter = any(r.sampling.top_k > 0 or r.sampling.top_p < 1.0
                      for r in reqs)
     if has_filter and logits.is_cuda:
-        # native fused kernel: per-row thresholds, no sort, no host sync
+        # native fused kernel: exact per-row thresholds, top-k then the
+        # nucleus of the survivors as in _filter_topk_topp; no sort, no
+        # host sync
         tk = torch.tensor([r.sampling.top_k for r in reqs],
                           dtype=torch.int32, device=logits.device)
         tp = torch.tensor([r.sampling.top_p for r in reqs],

@@ -176,6 +176,46 @@ def greedy_sample(logits: torch.Tensor) -> torch.Tensor:
     return logits.argmax(dim=-1).to(torch.int32)
 
 
+def topkp_keep_mask(logits: torch.Tensor, top_k, top_p) -> torch.Tensor:
+    """The set a top-k / top-p filtered sampler may draw from: bool [B, V],
+    computed per row in float64. `top_k` and `top_p` are scalars or [B].
+
+    top-k first (off for k <= 0 or k >= V): every entry >= the k-th largest
+    logit survives, so a tie at the boundary is kept whole. Then top-p (off
+    for p >= 1) on the softmax over the survivors only: a token is kept iff
+    the mass of the tokens strictly above it is <= top_p. Tokens with equal
+    logits stand or fall together (a sort would split them by its own
+    order), and the argmax is always kept, whatever top_p is. -inf entries
+    are never kept unless the whole row is -inf. This is the keep set of
+    engine/sampling.py::_filter_topk_topp wherever no tie straddles the
+    nucleus boundary, and the contract of the HIP topkp_sample kernel."""
+    x = logits.detach().cpu().double()
+    B, V = x.shape
+    ks = torch.as_tensor(top_k).reshape(-1).expand(B).tolist()
+    ps = torch.as_tensor(top_p).double().reshape(-1).expand(B).tolist()
+    mask = torch.zeros(B, V, dtype=torch.bool)
+    for b in range(B):
+        row, k, p = x[b], int(ks[b]), ps[b]
+        keep = row > float("-inf")
+        if not bool(keep.any()):
+            keep = torch.ones(V, dtype=torch.bool)
+        if 0 < k < V:
+            keep &= row >= torch.topk(row, k).values[-1]
+        if p < 1.0:
+            srt, idx = torch.sort(row.masked_fill(~keep, float("-inf")),
+                                  descending=True, stable=True)
+            prob = torch.softmax(srt, dim=-1)
+            above = prob.cumsum(-1) - prob      # mass before each position
+            # every member of a run of equal logits takes the run's first
+            _, run, counts = torch.unique_consecutive(
+                srt, return_inverse=True, return_counts=True)
+            above = above[(counts.cumsum(0) - counts)[run]]
+            nucleus = (above <= p) | (run == 0)
+            keep &= torch.zeros(V, dtype=torch.bool).scatter(0, idx, nucleus)
+        mask[b] = keep
+    return mask
+
+
 # --------------------------------------------------------------------------
 # batched LoRA: every row picks its adapter from a bank by slot
 def lora_shrink(t, x, A_bank, slots, ranks):

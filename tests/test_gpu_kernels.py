@@ -412,27 +412,28 @@ def test_topkp_sample_membership_and_determinism():
     degenerates to argmax."""
     torch.manual_seed(3)
     V = 5000
-    params = [(0, 1.0), (4, 1.0), (0, 0.3), (50, 0.9), (1, 1.0), (8, 0.5)]
+    # (8, 0.8): the nucleus is taken over the renormalised top-8, where the
+    # first token alone holds 0.64, so a top_p of 0.5 would keep only it
+    params = [(0, 1.0), (4, 1.0), (0, 0.3), (50, 0.9), (1, 1.0), (8, 0.8)]
     B = len(params)
     logits = (torch.randn(B, V) * 3).float().cuda()
     tk = torch.tensor([k for k, _ in params], dtype=torch.int32).cuda()
     tp = torch.tensor([p for _, p in params], dtype=torch.float32).cuda()
     inv_t = torch.ones(B).cuda()
-    # reference allowed set with a relative tolerance at the threshold
-    # (CPU exp vs GPU __expf can disagree on the exact boundary token)
-    allowed = []
+    # the exact reference set, with no tolerance at the threshold: every
+    # top_p must be 1e-3 or more away from the float64 cumulative mass of
+    # the top-k survivors either side (the kernel's fp32 mass is good to
+    # ~2e-6), and no k-th / (k+1)-th logit pair closer than 1e-3
     for i, (k, p) in enumerate(params):
-        probs = torch.softmax(logits[i].cpu().double(), -1)
-        sp, _ = torch.sort(probs, descending=True)
-        thr = 0.0
+        srt = logits[i].cpu().double().sort(descending=True).values
         if 0 < k < V:
-            thr = max(thr, sp[k - 1].item())
+            assert float(srt[k - 1] - srt[k]) >= 1e-3
+            srt = srt[:k]
         if p < 1.0:
-            cum = torch.cumsum(sp, 0)
-            j = int(torch.searchsorted(cum, p).item())  # first cum >= p
-            thr = max(thr, sp[min(j, V - 1)].item())
-        keep = probs >= thr * (1 - 1e-3)
-        allowed.append(set(torch.nonzero(keep).flatten().tolist()))
+            cum = torch.softmax(srt, -1).cumsum(-1)
+            assert float((cum - float(tp[i])).abs().min()) >= 1e-3
+    mask = torch_ref.topkp_keep_mask(logits, tk.cpu(), tp.cpu())
+    allowed = [set(torch.nonzero(m).flatten().tolist()) for m in mask]
     argmax = logits.argmax(-1).cpu().tolist()
     seen = [set() for _ in range(B)]
     for seed in range(40):
