@@ -460,6 +460,132 @@ def bench_lora(T=16, R=64):
         del As, Bs
 
 
+# --------------------------------------------------------------------------
+# Routed MoE decode (csrc/moe_decode.hip) at Mixtral-8x7B shapes
+MIXTRAL = dict(D=4096, I=14336, E=8, topk=2)
+
+
+def _event_time(g, n):
+    """Seconds per replay of graph g over n back-to-back replays, by device
+    events."""
+    start, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+    start.record()
+    for _ in range(n):
+        g.replay()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) * 1e-3 / n
+
+
+def _capture(fn):
+    fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g), torch.no_grad():
+        fn()
+    g.replay()
+    torch.cuda.synchronize()
+    return g
+
+
+def _replays_for(g, window):
+    """How many replays fill `window` seconds."""
+    return max(5, int(window / _event_time(g, 5)) + 1)
+
+
+def bench_moe_decode(Ts=(1, 4, 16, 64), rounds=3, window=0.5):
+    """One MoEMLP at Mixtral-8x7B shapes: the padded-bmm route (the default),
+    the grouped-kernel route (DYNAMO_MOE_BMM=0) and the routed kernels
+    (DYNAMO_MOE_FUSED=1), each a captured graph, alternated `rounds` times in
+    windows of >= `window` s. us per block (min - max over the rounds) and the
+    weight bytes of the experts the routing makes live over the best time."""
+    from dynamo_amd.engine.config import ModelConfig
+    from dynamo_amd.models.layers import TPContext, linear
+    from dynamo_amd.models.mixtral import MoEMLP
+    m = MIXTRAL
+    cfg = ModelConfig(name="mixtral-8x7b-moe", arch="mixtral",
+                      hidden_size=m["D"], intermediate_size=m["I"],
+                      num_experts=m["E"], num_experts_per_tok=m["topk"])
+    moe = MoEMLP(cfg, TPContext(), "cuda", torch.bfloat16)
+    envs_of = {"bmm": {}, "seg": {"DYNAMO_MOE_BMM": "0"},
+               "fused": {"DYNAMO_MOE_FUSED": "1"}}
+    for T in Ts:
+        x = torch.randn(T, m["D"], dtype=torch.bfloat16, device="cuda")
+        topi = ops.topk_gating(linear(x, moe.router).float(), m["topk"])[1]
+        live = int(topi.unique().numel())
+        gb = live * 3 * m["I"] * m["D"] * 2 / 1e9
+        graphs, outs = {}, {}
+        for route, env in envs_of.items():
+            for k in ("DYNAMO_MOE_BMM", "DYNAMO_MOE_FUSED"):
+                os.environ.pop(k, None)
+            os.environ.update(env)
+            with torch.no_grad():
+                outs[route] = moe.forward(x).float()
+            graphs[route] = _capture(lambda: moe.forward(x))
+            os.environ.pop(next(iter(env), ""), None)
+        n = {r: _replays_for(g, window) for r, g in graphs.items()}
+        ts = {r: [] for r in graphs}
+        for _ in range(rounds):
+            for r, g in graphs.items():
+                ts[r].append(_event_time(g, n[r]))
+        diff = float((outs["fused"] - outs["bmm"]).abs().max()
+                     / outs["bmm"].abs().max())
+        row = " | ".join(
+            f"{r} {min(v)*1e6:7.1f}-{max(v)*1e6:7.1f} us "
+            f"{gb/min(v):5.0f} GB/s" for r, v in ts.items())
+        print(f"moe_decode T={T:2d} live {live} ({gb:.2f} GB): {row} | "
+              f"bmm/fused {min(ts['bmm'])/min(ts['fused']):4.2f}x | "
+              f"max |fused - bmm| / max |bmm| {diff:.1e}")
+
+
+def bench_moe_decode_sweep(Ts=(1, 16, 64), tps=(1, 2, 4, 8), window=0.15):
+    """Every point of ops.MOE_DECODE_CONFIGS on Mixtral-8x7B's gate/up
+    (SwiGLU epilogue, gathered A) and down (weighted epilogue + combine)
+    expert weights and their TP shards of I: picks ops.MOE_DECODE_SHAPES.
+    The pick for T <= 16 is the lowest sum of times relative to the best at
+    T = 1 and T = 16, the pick for T > 16 the fastest at T = 64."""
+    m = MIXTRAL
+    E, K, D = m["E"], m["topk"], m["D"]
+    for tp in tps:
+        I = m["I"] // tp
+        wgu = torch.randn(E, 2 * I, D, dtype=torch.bfloat16, device="cuda")
+        wd = torch.randn(E, D, I, dtype=torch.bfloat16, device="cuda")
+        for name, w in (("gate_up", wgu), ("down", wd)):
+            N, Kd = w.shape[1:]
+            fits = [c for c in ops.MOE_DECODE_CONFIGS
+                    if Kd % (c[0] * 64 * c[1]) == 0]
+            t = {}
+            for T in Ts:
+                logits = torch.randn(T, E, device="cuda")
+                topw, topi = ops.topk_gating(logits, K)
+                seg, pair = ops.moe_route(topi, E)
+                live = int(topi.unique().numel())
+                x = torch.randn(T, D, dtype=torch.bfloat16, device="cuda")
+                act = torch.randn(T * K, I, dtype=torch.bfloat16,
+                                  device="cuda")
+                for c in fits:
+                    if name == "gate_up":
+                        fn = lambda: ops.moe_routed_gemm(  # noqa: E731
+                            x, w, seg, pair, K, gather=True, glu=True, cfg=c)
+                    else:
+                        fn = lambda: ops.moe_down_combine(  # noqa: E731
+                            act, w, seg, pair, topw, cfg=c)
+                    g = _capture(fn)
+                    t[T, c] = _event_time(g, _replays_for(g, window))
+                best = min(t[T, c] for c in fits)
+                gb = live * N * Kd * 2 / 1e9
+                print(f"moe_decode_sweep {name} ({N}, {Kd}) T={T:2d} live "
+                      f"{live}: " + " | ".join(
+                          f"{c} {t[T, c]*1e6:6.1f}" for c in fits)
+                      + f" us; best {gb/best:5.0f} GB/s")
+            rel = {c: sum(t[T, c] / min(t[T, d] for d in fits)
+                          for T in Ts if T <= 16) for c in fits}
+            small = min(fits, key=rel.get)
+            large = min(fits, key=lambda c: t[max(Ts), c])
+            print(f"moe_decode_sweep PICK ({N}, {Kd}): ({small}, {large}),")
+        del wgu, wd
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--which", default="all")
@@ -502,6 +628,12 @@ if __name__ == "__main__":
         bench_skinny_gemm(M=64)
     if w in ("all", "lora"):
         bench_lora()
+    if w in ("all", "moe_decode"):
+        bench_moe_decode()
+    if w == "moe_decode_sweep":
+        # every launchable routed-GEMM configuration per Mixtral shape:
+        # picks ops.MOE_DECODE_SHAPES
+        bench_moe_decode_sweep()
     if w == "fp8sweep":
         # every launchable W8A16 configuration per shape: picks
         # ops.FP8_GEMM_SHAPES

@@ -91,6 +91,16 @@ void moe_grouped_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
 void moe_grouped_gemm_seg(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                           torch::Tensor seg_start, int64_t max_tokens);
 void topk_gating(torch::Tensor topw, torch::Tensor topi, torch::Tensor logits);
+// moe_decode.hip
+void moe_route(torch::Tensor topi, torch::Tensor seg_start,
+               torch::Tensor pair_of);
+void moe_routed_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
+                     torch::Tensor seg_start, torch::Tensor pair_of,
+                     c10::optional<torch::Tensor> topw, int64_t topk,
+                     bool gather, int64_t epilogue, int64_t wpb, int64_t u,
+                     int64_t nt);
+void moe_combine(torch::Tensor out, torch::Tensor part, int64_t topk);
+std::vector<std::tuple<int, int, int>> moe_decode_configs();
 // ipc.hip
 torch::Tensor ipc_alloc(int64_t nbytes, int64_t device);
 py::bytes ipc_export(torch::Tensor t);
@@ -202,6 +212,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_grouped_gemm", &moe_grouped_gemm);
   m.def("moe_grouped_gemm_seg", &moe_grouped_gemm_seg);
   m.def("topk_gating", &topk_gating);
+  // routed MoE decode (T <= 64, top-k <= 8, E <= 64, bf16 expert weights):
+  // the stable expert grouping of topi, the expert-grouped skinny GEMM
+  // (epilogue 0 = bf16, 1 = fused SwiGLU, 2 = fp32 times the gate weight,
+  // scattered to pair order) and the per-token sum of the weighted rows;
+  // they raise on anything they do not handle - dispatch lives in
+  // ops.moe_decode_mlp
+  m.def("moe_route", &moe_route, py::arg("topi"), py::arg("seg_start"),
+        py::arg("pair_of"));
+  m.def("moe_routed_gemm", &moe_routed_gemm, py::arg("out"), py::arg("a"),
+        py::arg("w"), py::arg("seg_start"), py::arg("pair_of"),
+        py::arg("topw"), py::arg("topk"), py::arg("gather"),
+        py::arg("epilogue"), py::arg("wpb") = 1, py::arg("u") = 1,
+        py::arg("nt") = 2);
+  m.def("moe_combine", &moe_combine, py::arg("out"), py::arg("part"),
+        py::arg("topk"));
+  // [(WPB, U, NT), ...] moe_routed_gemm can launch
+  m.def("moe_decode_configs", &moe_decode_configs);
   m.def("ipc_alloc", &ipc_alloc);
   m.def("ipc_export", &ipc_export);
   m.def("ipc_open", &ipc_open);

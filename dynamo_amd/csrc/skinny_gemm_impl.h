@@ -444,7 +444,9 @@ __global__ __launch_bounds__(WPB * 64) void skinny_gemm_kernel(
 
 // out[n, k] = bf16_rne(float(wq[n, k]) * scale[n]); one thread converts
 // 16 consecutive k (one 16 B load, two 16 B stores). Requires K % 16 == 0.
-__global__ __launch_bounds__(256) void fp8_dequant_kernel(
+// static, like mxfp4_dequant_kernel: more than one source file of the
+// extension includes this header.
+static __global__ __launch_bounds__(256) void fp8_dequant_kernel(
     short* __restrict__ out, const unsigned char* __restrict__ wq,
     const float* __restrict__ scale, long long N, long long K) {
   const long long chunks = K / 16;
@@ -475,7 +477,7 @@ __global__ __launch_bounds__(256) void fp8_dequant_kernel(
 
 // out[n, k] = bf16(W_eff[n, k]); one thread converts one 32-k MX block (one
 // 16 B load, one scale byte, four 16 B stores). Requires K % 32 == 0.
-__global__ __launch_bounds__(256) void mxfp4_dequant_kernel(
+static __global__ __launch_bounds__(256) void mxfp4_dequant_kernel(
     short* __restrict__ out, const unsigned char* __restrict__ q,
     const unsigned char* __restrict__ scale, long long blocks) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

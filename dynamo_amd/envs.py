@@ -52,6 +52,11 @@ ENV_VARS = {
         "W8A16) | mxfp4 (OCP microscaling FP4 projection weights: e2m1 codes "
         "with one e8m0 scale per 32 k, W4A16)",
     "DYNAMO_MOE_BMM": "0 = grouped-kernel MoE decode instead of padded bmm",
+    "DYNAMO_MOE_FUSED":
+        "1 = routed MoE decode for T <= 64 (csrc/moe_decode.hip: route, "
+        "expert-grouped gate/up GEMM with SwiGLU, weighted down GEMM, "
+        "combine; idle experts' weights are not read). Default: the padded "
+        "bmm route",
     "DYNAMO_MOE_MFMA": "0 = VALU grouped MoE GEMM",
     "DYNAMO_MOE_GRAPHS": "0 = exclude MoE layers from hipGraph capture",
     "DYNAMO_ROCTX": "1 = roctx range annotations for rocprofv3 traces",

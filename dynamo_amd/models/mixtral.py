@@ -9,7 +9,7 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
-from dynamo_amd import ops
+from dynamo_amd import envs, ops
 from .layers import (AttnMetadata, Attention, TPContext, init_const,
                      init_weight, linear)
 
@@ -75,6 +75,16 @@ class MoEMLP(torch.nn.Module):
         T, D = x.shape
         logits = linear(x, self.router).float()            # [T, E]
         topw, topi = ops.topk_gating(logits, self.topk)    # [T, k]
+        if (x.is_cuda and not self.ep
+                and envs.get("DYNAMO_MOE_FUSED", False, bool)
+                and ops.moe_decode_ready(x, self.topk, self.w_gate_up,
+                                         self.w_down)):
+            # opt-in routed decode (csrc/moe_decode.hip): route, gate/up
+            # GEMM + SwiGLU, weighted down GEMM, combine. Only live experts'
+            # weights are read; device-side and static, so hipGraph-safe.
+            out = ops.moe_decode_mlp(x, topw, topi, self.w_gate_up,
+                                     self.w_down)
+            return self.tp.all_reduce(out)
         topw = topw.to(x.dtype)
 
         out = torch.zeros_like(x)

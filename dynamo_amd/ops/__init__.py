@@ -613,6 +613,137 @@ def moe_grouped_gemm_seg(x, w, seg_start, max_tokens):
     return y
 
 
+# --------------------------------------------------------------------------
+# Routed MoE decode (csrc/moe_decode.hip): T <= 64 tokens, top-k <= 8 of
+# E <= 64 experts, bf16 expert weights. Route, expert-grouped gate/up GEMM with
+# SwiGLU in its epilogue, expert-grouped down GEMM weighted by the gate
+# weights, per-token combine: four launches, and only live experts' weights
+# are read. Opt-in through DYNAMO_MOE_FUSED=1 (models/mixtral.py).
+MOE_DECODE_MAX_T, MOE_DECODE_MAX_TOPK, MOE_DECODE_MAX_E = 64, 8, 64
+# (WPB, U, NT) points of moe_routed_gemm; it needs K % (WPB * 64 * U) == 0.
+# A copy of the kernel file's MOE_DECODE_CONFIGS that tests can read without
+# the extension; they check it against hip().moe_decode_configs().
+MOE_DECODE_CONFIGS: tuple = (
+    (1, 1, 2), (1, 2, 2), (1, 2, 4), (2, 2, 2), (4, 1, 2), (4, 2, 2),
+    (4, 1, 4), (8, 1, 2),
+)
+# (N, K) of an expert's weight -> ((WPB, U, NT) for T <= 16, for T > 16):
+# Mixtral-8x7B's gate/up (2I, D) and down (D, I) and their TP-2/4/8 shards of
+# I; the winners of `kernel_bench.py --which moe_decode_sweep`
+# (profiles/README.md, "Routed MoE decode").
+MOE_DECODE_SHAPES: dict = {
+    (28672, 4096): ((8, 1, 2), (4, 1, 4)),    # gate/up
+    (14336, 4096): ((4, 2, 2), (4, 1, 4)),    # gate/up, TP 2
+    (7168, 4096): ((8, 1, 2), (4, 1, 4)),     # gate/up, TP 4
+    (3584, 4096): ((4, 2, 2), (4, 1, 4)),     # gate/up, TP 8
+    (4096, 14336): ((4, 2, 2), (4, 1, 4)),    # down
+    (4096, 7168): ((8, 1, 2), (4, 1, 4)),     # down, TP 2
+    (4096, 3584): ((4, 1, 2), (4, 1, 4)),     # down, TP 4
+    (4096, 1792): ((4, 1, 2), (4, 1, 4)),     # down, TP 8
+}
+
+
+def moe_decode_config(N: int, K: int, T: int):
+    """The (WPB, U, NT) the routed GEMM runs an expert weight [N, K] at for T
+    tokens: the shape's MOE_DECODE_SHAPES entry, else the deepest point of the
+    table (largest K step WPB * 64 * U, the earlier one among equals) that
+    divides K. None if the kernel does not take the shape."""
+    if not (1 <= T <= MOE_DECODE_MAX_T and N >= 16 and N % 16 == 0
+            and K >= 64 and K % 64 == 0):
+        return None
+    entry = MOE_DECODE_SHAPES.get((N, K))
+    if entry is not None:
+        return entry[0 if T <= 16 else 1]
+    fits = [c for c in MOE_DECODE_CONFIGS if K % (c[0] * 64 * c[1]) == 0]
+    return max(fits, key=lambda c: c[0] * c[1])
+
+
+def moe_route(topi: torch.Tensor, E: int):
+    """topi [T, K] int32 -> (seg_start [E + 1], pair_of [T K]), int32: the
+    pairs p = t K + j grouped by expert, ascending within an expert (equal to
+    argsort(topi.flatten(), stable=True)), and each expert's first sorted
+    position."""
+    if not topi.is_cuda:
+        return torch_ref.moe_route(topi, E)
+    seg_start = torch.empty(E + 1, dtype=torch.int32, device=topi.device)
+    pair_of = torch.empty(topi.numel(), dtype=torch.int32, device=topi.device)
+    hip().moe_route(topi.contiguous(), seg_start, pair_of)
+    return seg_start, pair_of
+
+
+def _moe_cfg(w, T, cfg):
+    cfg = cfg or moe_decode_config(w.shape[1], w.shape[2], T)
+    if cfg is None:
+        raise ValueError(f"no routed MoE GEMM for expert weights "
+                         f"{tuple(w.shape)} at T = {T}")
+    return cfg
+
+
+def moe_routed_gemm(a, w, seg_start, pair_of, topk: int, *, gather: bool,
+                    glu: bool, cfg=None):
+    """Sorted row i of expert e times w[e]^T, w [E, N, K] -> bf16 [T topk, N]
+    in sorted order. gather: a is x [T, K] and row i is x[pair_of[i] // topk];
+    else a is [T topk, K], already sorted. glu: w[e] is a gate/up weight and
+    the result is [T topk, N / 2] = silu_mul of the plain one, equal bits."""
+    if not a.is_cuda:
+        return torch_ref.moe_routed_gemm(a, w, seg_start, pair_of, topk,
+                                         gather, glu)
+    P = pair_of.numel()
+    cfg = _moe_cfg(w, P // topk, cfg)
+    y = torch.empty(P, w.shape[1] // 2 if glu else w.shape[1], dtype=a.dtype,
+                    device=a.device)
+    hip().moe_routed_gemm(y, a, w, seg_start, pair_of, None, topk, gather,
+                          1 if glu else 0, *cfg)
+    return y
+
+
+def moe_down_combine(act, w_down, seg_start, pair_of, topw, cfg=None):
+    """out[t] = bf16(sum_j topw[t, j] * act[row of pair (t, j)] @ w_down[e]^T)
+    -> [T, D]: act [T topk, I] in sorted order, topw [T, topk] fp32. The GEMM
+    writes fp32 rows already multiplied by the gate weight, the combine sums
+    them in ascending j and rounds once."""
+    if not act.is_cuda:
+        return torch_ref.moe_down_combine(act, w_down, seg_start, pair_of,
+                                          topw)
+    T, topk = topw.shape
+    cfg = _moe_cfg(w_down, T, cfg)
+    part = torch.empty(T * topk, w_down.shape[1], dtype=torch.float32,
+                       device=act.device)
+    hip().moe_routed_gemm(part, act, w_down, seg_start, pair_of,
+                          topw.contiguous(), topk, False, 2, *cfg)
+    out = torch.empty(T, w_down.shape[1], dtype=act.dtype, device=act.device)
+    hip().moe_combine(out, part, topk)
+    return out
+
+
+def moe_decode_ready(x, topk: int, w_gate_up, w_down) -> bool:
+    """Whether moe_decode_mlp takes the call on the GPU: the kernels' limits
+    on T, top-k and E, bf16, and a configuration for both GEMMs."""
+    T = x.shape[0]
+    E, N, K = w_gate_up.shape
+    return (x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16
+            and w_gate_up.dtype == torch.bfloat16
+            and w_down.dtype == torch.bfloat16
+            and 1 <= T <= MOE_DECODE_MAX_T
+            and 1 <= topk <= MOE_DECODE_MAX_TOPK and E <= MOE_DECODE_MAX_E
+            and N % 32 == 0 and x.is_contiguous()
+            and w_gate_up.is_contiguous() and w_down.is_contiguous()
+            and moe_decode_config(N, K, T) is not None
+            and moe_decode_config(w_down.shape[1], w_down.shape[2], T)
+            is not None)
+
+
+def moe_decode_mlp(x, topw, topi, w_gate_up, w_down):
+    """The routed expert MLP of a decode step: x [T, D] bf16, topw / topi
+    [T, topk] fp32 / int32 of topk_gating, w_gate_up [E, 2I, D] (gate rows
+    first), w_down [E, D, I] -> [T, D] bf16."""
+    topk = topi.shape[1]
+    seg_start, pair_of = moe_route(topi, w_gate_up.shape[0])
+    act = moe_routed_gemm(x, w_gate_up, seg_start, pair_of, topk,
+                          gather=True, glu=True)
+    return moe_down_combine(act, w_down, seg_start, pair_of, topw.float())
+
+
 def gather_pages(staging, cache, page_ids):
     if cache.is_cuda:
         hip().gather_pages(staging, cache, page_ids)

@@ -307,3 +307,51 @@ def apply_logit_processors(logits, counts, slots, params, bias=None):
             drop = (row - row.max()) / temp < torch.log(min_p)
             row.masked_fill_(drop, float("-inf"))
     return logits
+
+
+# --------------------------------------------------------------------------
+# Routed MoE decode: the contract of csrc/moe_decode.hip. A pair is
+# p = t * topk + j; pair_of lists the pairs grouped by expert (stable), and
+# expert e owns sorted positions seg_start[e] .. seg_start[e + 1] - 1.
+def moe_route(topi, E):
+    """topi [T, K] -> (seg_start [E + 1] int32, pair_of [T K] int32); indices
+    outside [0, E) are clamped into it, as in the kernel."""
+    flat = topi.reshape(-1).long().clamp(0, E - 1)
+    pair_of = torch.argsort(flat, stable=True).to(torch.int32)
+    seg_start = torch.zeros(E + 1, dtype=torch.int32, device=topi.device)
+    seg_start[1:] = torch.cumsum(torch.bincount(flat, minlength=E), 0)
+    return seg_start, pair_of
+
+
+def _moe_segments(a, w, seg_start, pair_of, topk, gather):
+    """fp32 [P, N]: sorted row i times its expert's weight."""
+    rows = a[pair_of.long() // topk] if gather else a
+    out = torch.zeros(pair_of.numel(), w.shape[1], dtype=torch.float32,
+                      device=a.device)
+    seg = seg_start.tolist()
+    for e in range(w.shape[0]):
+        lo, hi = seg[e], seg[e + 1]
+        if hi > lo:
+            out[lo:hi] = rows[lo:hi].float() @ w[e].float().T
+    return out
+
+
+def moe_routed_gemm(a, w, seg_start, pair_of, topk, gather, glu):
+    """[P, N] (or [P, N / 2] = silu_mul of it if glu) in a's dtype, sorted
+    order."""
+    y = _moe_segments(a, w, seg_start, pair_of, topk, gather).to(a.dtype)
+    return silu_mul(y) if glu else y
+
+
+def moe_down_combine(act, w_down, seg_start, pair_of, topw):
+    """out[t] = dtype(sum_j topw[t, j] * (act row of pair (t, j)) @
+    w_down[e]^T): fp32 throughout, ascending j, one rounding."""
+    T, topk = topw.shape
+    y = _moe_segments(act, w_down, seg_start, pair_of, topk, False)
+    part = torch.empty_like(y)
+    part[pair_of.long()] = y * topw.reshape(-1)[pair_of.long()].unsqueeze(-1)
+    part = part.view(T, topk, -1)
+    out = part[:, 0].clone()
+    for j in range(1, topk):
+        out += part[:, j]
+    return out.to(act.dtype)

@@ -29,6 +29,7 @@ hip_sources = [
         "sampling.hip",
         "logits_process.hip",
         "moe.hip",
+        "moe_decode.hip",
         "lora.hip",
         "ipc.hip",
         "probe.hip",
