@@ -538,22 +538,33 @@ def bench_moe_decode(Ts=(1, 4, 16, 64), rounds=3, window=0.5):
               f"max |fused - bmm| / max |bmm| {diff:.1e}")
 
 
-def bench_moe_decode_sweep(Ts=(1, 16, 64), tps=(1, 2, 4, 8), window=0.15):
+def bench_moe_decode_sweep(Ts=(1, 16, 64), tps=(1, 2, 4, 8), window=0.15,
+                           fmts=("bf16", "fp8", "mxfp4")):
     """Every point of ops.MOE_DECODE_CONFIGS on Mixtral-8x7B's gate/up
     (SwiGLU epilogue, gathered A) and down (weighted epilogue + combine)
     expert weights and their TP shards of I: picks ops.MOE_DECODE_SHAPES.
     The pick for T <= 16 is the lowest sum of times relative to the best at
-    T = 1 and T = 16, the pick for T > 16 the fastest at T = 64."""
+    T = 1 and T = 16, the pick for T > 16 the fastest at T = 64.
+    With quantised formats in `fmts` the same shapes, T and routings run the
+    fp8 / mxfp4 kernels on the quantised weights next to the bf16 column
+    (picks ops.MOE_DECODE_FP8_SHAPES / MOE_DECODE_MXFP4_SHAPES); live bytes
+    count codes and scales."""
     m = MIXTRAL
     E, K, D = m["E"], m["topk"], m["D"]
+    holder = {"bf16": lambda w: w,
+              "fp8": ops.Fp8ExpertWeight.from_tensor,
+              "mxfp4": ops.Mxfp4ExpertWeight.from_tensor}
+    bytes_per_weight = {"bf16": 2.0, "fp8": 1.0, "mxfp4": 0.5 + 1 / 32}
     for tp in tps:
         I = m["I"] // tp
-        wgu = torch.randn(E, 2 * I, D, dtype=torch.bfloat16, device="cuda")
-        wd = torch.randn(E, D, I, dtype=torch.bfloat16, device="cuda")
-        for name, w in (("gate_up", wgu), ("down", wd)):
-            N, Kd = w.shape[1:]
-            fits = [c for c in ops.MOE_DECODE_CONFIGS
-                    if Kd % (c[0] * 64 * c[1]) == 0]
+        for name, shape in (("gate_up", (E, 2 * I, D)), ("down", (E, D, I))):
+            N, Kd = shape[1:]
+            w16 = torch.randn(shape, dtype=torch.bfloat16, device="cuda")
+            ws = {f: holder[f](w16) for f in fmts}
+            del w16
+            fits = {f: [c for c in ops.MOE_DECODE_FORMATS[f][1]
+                        if Kd % (c[0] * ops.MOE_DECODE_FORMATS[f][0]
+                                 * c[1]) == 0] for f in fmts}
             t = {}
             for T in Ts:
                 logits = torch.randn(T, E, device="cuda")
@@ -563,27 +574,33 @@ def bench_moe_decode_sweep(Ts=(1, 16, 64), tps=(1, 2, 4, 8), window=0.15):
                 x = torch.randn(T, D, dtype=torch.bfloat16, device="cuda")
                 act = torch.randn(T * K, I, dtype=torch.bfloat16,
                                   device="cuda")
-                for c in fits:
-                    if name == "gate_up":
-                        fn = lambda: ops.moe_routed_gemm(  # noqa: E731
-                            x, w, seg, pair, K, gather=True, glu=True, cfg=c)
-                    else:
-                        fn = lambda: ops.moe_down_combine(  # noqa: E731
-                            act, w, seg, pair, topw, cfg=c)
-                    g = _capture(fn)
-                    t[T, c] = _event_time(g, _replays_for(g, window))
-                best = min(t[T, c] for c in fits)
-                gb = live * N * Kd * 2 / 1e9
-                print(f"moe_decode_sweep {name} ({N}, {Kd}) T={T:2d} live "
-                      f"{live}: " + " | ".join(
-                          f"{c} {t[T, c]*1e6:6.1f}" for c in fits)
-                      + f" us; best {gb/best:5.0f} GB/s")
-            rel = {c: sum(t[T, c] / min(t[T, d] for d in fits)
-                          for T in Ts if T <= 16) for c in fits}
-            small = min(fits, key=rel.get)
-            large = min(fits, key=lambda c: t[max(Ts), c])
-            print(f"moe_decode_sweep PICK ({N}, {Kd}): ({small}, {large}),")
-        del wgu, wd
+                for f in fmts:
+                    w = ws[f]
+                    for c in fits[f]:
+                        if name == "gate_up":
+                            fn = lambda: ops.moe_routed_gemm(  # noqa: E731
+                                x, w, seg, pair, K, gather=True, glu=True,
+                                cfg=c)
+                        else:
+                            fn = lambda: ops.moe_down_combine(  # noqa: E731
+                                act, w, seg, pair, topw, cfg=c)
+                        g = _capture(fn)
+                        t[f, T, c] = _event_time(g, _replays_for(g, window))
+                    best = min(t[f, T, c] for c in fits[f])
+                    gb = live * N * Kd * bytes_per_weight[f] / 1e9
+                    print(f"moe_decode_sweep {f} {name} ({N}, {Kd}) T={T:2d} "
+                          f"live {live}: " + " | ".join(
+                              f"{c} {t[f, T, c]*1e6:6.1f}" for c in fits[f])
+                          + f" us; best {best*1e6:6.1f} us "
+                          f"{gb/best:5.0f} GB/s")
+            for f in fmts:
+                rel = {c: sum(t[f, T, c] / min(t[f, T, d] for d in fits[f])
+                              for T in Ts if T <= 16) for c in fits[f]}
+                small = min(fits[f], key=rel.get)
+                large = min(fits[f], key=lambda c: t[f, max(Ts), c])
+                print(f"moe_decode_sweep PICK {f} ({N}, {Kd}): "
+                      f"({small}, {large}),")
+            del ws
 
 
 if __name__ == "__main__":

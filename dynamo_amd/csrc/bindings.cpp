@@ -99,8 +99,22 @@ void moe_routed_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
                      c10::optional<torch::Tensor> topw, int64_t topk,
                      bool gather, int64_t epilogue, int64_t wpb, int64_t u,
                      int64_t nt);
+void moe_routed_gemm_fp8(torch::Tensor out, torch::Tensor a, torch::Tensor wq,
+                         torch::Tensor scale, torch::Tensor seg_start,
+                         torch::Tensor pair_of,
+                         c10::optional<torch::Tensor> topw, int64_t topk,
+                         bool gather, int64_t epilogue, int64_t wpb, int64_t u,
+                         int64_t nt);
+void moe_routed_gemm_mxfp4(torch::Tensor out, torch::Tensor a, torch::Tensor q,
+                           torch::Tensor scale, torch::Tensor seg_start,
+                           torch::Tensor pair_of,
+                           c10::optional<torch::Tensor> topw, int64_t topk,
+                           bool gather, int64_t epilogue, int64_t wpb,
+                           int64_t u, int64_t nt);
 void moe_combine(torch::Tensor out, torch::Tensor part, int64_t topk);
 std::vector<std::tuple<int, int, int>> moe_decode_configs();
+std::map<std::string, std::vector<std::tuple<int, int, int>>>
+moe_decode_quant_configs();
 // ipc.hip
 torch::Tensor ipc_alloc(int64_t nbytes, int64_t device);
 py::bytes ipc_export(torch::Tensor t);
@@ -229,6 +243,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("topk"));
   // [(WPB, U, NT), ...] moe_routed_gemm can launch
   m.def("moe_decode_configs", &moe_decode_configs);
+  // moe_routed_gemm for quantised expert weights: codes [E, N, K] e4m3 with
+  // scale fp32 [E, N], or codes uint8 [E, N, K / 2] with e8m0 scale
+  // [E, N, K / 32]; same epilogues, their own (WPB, U, NT) tables
+  m.def("moe_routed_gemm_fp8", &moe_routed_gemm_fp8, py::arg("out"),
+        py::arg("a"), py::arg("wq"), py::arg("scale"), py::arg("seg_start"),
+        py::arg("pair_of"), py::arg("topw"), py::arg("topk"),
+        py::arg("gather"), py::arg("epilogue"), py::arg("wpb") = 1,
+        py::arg("u") = 1, py::arg("nt") = 2);
+  m.def("moe_routed_gemm_mxfp4", &moe_routed_gemm_mxfp4, py::arg("out"),
+        py::arg("a"), py::arg("q"), py::arg("scale"), py::arg("seg_start"),
+        py::arg("pair_of"), py::arg("topw"), py::arg("topk"),
+        py::arg("gather"), py::arg("epilogue"), py::arg("wpb") = 1,
+        py::arg("u") = 1, py::arg("nt") = 2);
+  // {"fp8" | "mxfp4": [(WPB, U, NT), ...]} they can launch
+  m.def("moe_decode_quant_configs", &moe_decode_quant_configs);
   m.def("ipc_alloc", &ipc_alloc);
   m.def("ipc_export", &ipc_export);
   m.def("ipc_open", &ipc_open);

@@ -1,6 +1,7 @@
 // Routed MoE decode for MI355X/gfx950: T <= 64 tokens, top-K of E experts,
-// bf16 expert weights. Three kernels replace the sort / pad / bmm / gather /
-// index_add chain of MoEMLP.forward's decode branch:
+// bf16, fp8 (W8A16) or mxfp4 (W4A16) expert weights. Three kernels replace
+// the sort / pad / bmm / gather / index_add chain of MoEMLP.forward's decode
+// branch:
 //
 //   moe_route_kernel        topi [T, K] -> seg_start [E + 1], pair_of [T K]
 //   moe_skinny_gemm_kernel  one expert-grouped skinny GEMM per projection
@@ -36,9 +37,17 @@
 //             is in exactly one segment, so part is fully written.
 // Static grids on the current stream, no host sync and no allocation: the
 // route captures into the decode hipGraph.
+//
+// Quantised experts (ops.Fp8ExpertWeight, ops.Mxfp4ExpertWeight) run
+// moe_skinny_gemm_q_kernel in the GEMM's place: the Fp8Coal / Mxfp4Coal W
+// streams of the same header, per-expert scales, and the segment's rows split
+// into chunks of at most 32 on grid.z (described at the kernel). moe_route
+// and moe_combine serve every format.
 #include "skinny_gemm_impl.h"
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <map>
+#include <string>
 
 namespace moe_decode {
 
@@ -323,6 +332,262 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(
   *reinterpret_cast<short8*>(out + (size_t)t * D + c) = o;
 }
 
+// The routed GEMM for quantised expert weights: F is Fp8Coal (W8A16, codes
+// [E, N, K] e4m3, scale fp32 [E, N]) or Mxfp4Coal (W4A16, codes [E, N, K / 2]
+// bytes, scale e8m0 [E, N, K / 32]). Same contract as moe_skinny_gemm_kernel;
+// what differs:
+//   rows    the accumulator tiles are bounded by registers (FRAGS = 4 / 8 A
+//           fragments per m-tile and step), so MT <= 2 and grid.z carries the
+//           row chunk: block (x, e, z) owns rows [CH z, CH z + CH) of expert
+//           e's segment, CH = 16 MT, and returns before any load of codes or
+//           scales if CH z >= the segment's length, which an idle expert's 0
+//           always is. The launcher runs MT = 1, grid.z = 1 for T <= 16 and
+//           MT = 2, grid.z = ceil(T / 32) above, so an expert with at most
+//           32 rows streams its weights once and only a longer segment reads
+//           them again, once per further chunk. s and cnt below are the
+//           chunk's first sorted position and length; both depend on
+//           blockIdx and seg_start only, so they are block-uniform and every
+//           wave takes the same barriers.
+//   A       one step covers F::KSTEP k as F::FRAGS bf16x8 fragments per
+//           m-tile at F::x_k / F::x_step, the k order the format's b_frag
+//           produces.
+//   scales  fp8: scale[e, col] multiplies the fp32 accumulator in the
+//           epilogue, before the gate weight and the one rounding (GLU: gate
+//           and up by their own rows' scales, then rounded, then
+//           silu_mul_bf16). mxfp4: per step and column tile the destination
+//           lane loads the 8 scale bytes of its row (n = lane & 15) for the
+//           step's 256 k into F::Aux, on the default cache policy, and
+//           b_frag's v_cvt_scalef32_pk_bf16_fp4 applies them. Scale rows are
+//           clamped like W rows: tile columns past N read column N - 1.
+// Requires K % (WPB * F::KSTEP * U) == 0, N % 16 == 0 (N % 32 for GLU).
+template <class F, int WPB, int U, int NT, int MT, int EPI>
+__global__ __launch_bounds__(WPB * 64) void moe_skinny_gemm_q_kernel(
+    const short* __restrict__ a,          // gather: x [T, K]; direct: [P, K]
+    const typename F::welem* __restrict__ w,
+    const typename F::scale_t* __restrict__ scale,
+    const int* __restrict__ seg_start,    // [E + 1]
+    const int* __restrict__ pair_of,      // [P]
+    const float* __restrict__ topw,       // [P] fp32, WEIGHTED only
+    void* __restrict__ out,
+    int N, int K, int topk, int gather) {
+  using skinny::int4v;
+  typedef typename F::Aux Aux;
+  static_assert(MT <= 2, "longer segments go to further row chunks");
+  constexpr bool kGlu = EPI == GLU;
+  static_assert(!kGlu || NT % 2 == 0, "GLU pairs gate and up tiles");
+  constexpr int CH = 16 * MT;             // segment rows per block
+  const int e = blockIdx.y;
+  const int seg0 = seg_start[e];
+  const int z0 = blockIdx.z * CH;
+  const int left = seg_start[e + 1] - seg0 - z0;
+  if (left <= 0) return;                  // idle expert or chunk: nothing read
+  const int s = seg0 + z0;
+  const int cnt = left < CH ? left : CH;  // block-uniform
+
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;       // 0..WPB-1 = k-slice
+  const int lr = lane & 15;
+  const int lg = lane >> 4;
+  constexpr int NTO = kGlu ? NT / 2 : NT; // column tiles of the output
+  const int NO = kGlu ? N / 2 : N;        // columns of the output
+  const int n0 = (blockIdx.x * NTO) * 16;
+  if (n0 >= NO) return;
+  auto live = [&](int m) { return m == 0 || 16 * m < cnt; };
+
+  const int kw = K / WPB;
+  const int k0 = wid * kw;
+  const int steps = kw / F::KSTEP;
+
+  const short* xp[MT];
+#pragma unroll
+  for (int m = 0; m < MT; m++) {
+    const int r = m * 16 + lr;
+    const int pos = s + (r < cnt ? r : 0);
+    const int row = gather ? pair_of[pos] / topk : pos;
+    xp[m] = a + (size_t)row * K + k0 + F::x_k(lane);
+  }
+  const size_t erow = (size_t)e * N;      // the expert's first weight row
+  const typename F::welem* wp[NT][F::LOADS];
+#pragma unroll
+  for (int t = 0; t < NT; t++)
+#pragma unroll
+    for (int h = 0; h < F::LOADS; h++) {
+      int col = n0 + (t % NTO) * 16 + F::w_row(lane, h);
+      col = col < NO ? col : NO - 1;
+      if (kGlu && t >= NTO) col += NO;    // the up row of that column
+      wp[t][h] = w + (erow + col) * (K / F::WPACK) + k0 / F::WPACK +
+                 F::w_k(lane);
+    }
+  const typename F::scale_t* sp[NT];
+  if constexpr (F::BLOCK_SCALED) {
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+      int col = n0 + (t % NTO) * 16 + lr;
+      col = col < NO ? col : NO - 1;
+      if (kGlu && t >= NTO) col += NO;
+      sp[t] = scale + ((erow + col) * K + k0) / 32;
+    }
+  }
+  const typename F::Sel sel = F::sel(lane);
+
+  f32x4 acc[NT][MT];
+#pragma unroll
+  for (int t = 0; t < NT; t++)
+#pragma unroll
+    for (int m = 0; m < MT; m++) acc[t][m] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  bf16x8 abuf[U][MT][F::FRAGS];
+  int4v rbuf[NT][U][F::LOADS];
+  Aux auxbuf[NT][U];
+  auto load_x = [&](bf16x8 (&x)[MT][F::FRAGS], int d) {
+#pragma unroll
+    for (int m = 0; m < MT; m++)
+      if (live(m)) {
+#pragma unroll
+        for (int f = 0; f < F::FRAGS; f++)
+          x[m][f] = *reinterpret_cast<const bf16x8*>(xp[m] + d * F::KSTEP +
+                                                     F::x_step(f));
+      }
+  };
+  auto load_w = [&](int4v (&r)[F::LOADS], Aux& ax, int t, int d) {
+#pragma unroll
+    for (int h = 0; h < F::LOADS; h++)
+      r[h] = skinny::ldw<1>(wp[t][h] + d * (F::KSTEP / F::WPACK));
+    if constexpr (F::BLOCK_SCALED)
+      ax = *reinterpret_cast<const Aux*>(sp[t] + d * (F::KSTEP / 32));
+  };
+  auto consume = [&](const bf16x8 (&x)[MT][F::FRAGS],
+                     const int4v (&r)[F::LOADS], Aux ax, f32x4 (&c)[MT]) {
+#pragma unroll
+    for (int f = 0; f < F::FRAGS; f++) {
+      const bf16x8 b = F::b_frag(f, r, sel, ax);
+#pragma unroll
+      for (int m = 0; m < MT; m++)
+        if (live(m))
+          c[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[m][f], b, c[m],
+                                                         0, 0, 0);
+    }
+  };
+
+  // U steps in flight, as in moe_skinny_gemm_kernel.
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    load_x(abuf[u], u);
+#pragma unroll
+    for (int t = 0; t < NT; t++) load_w(rbuf[t][u], auxbuf[t][u], t, u);
+  }
+  for (int d = U; d < steps; d += U) {
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      bf16x8 x[MT][F::FRAGS];
+#pragma unroll
+      for (int m = 0; m < MT; m++)
+        if (live(m)) {
+#pragma unroll
+          for (int f = 0; f < F::FRAGS; f++) x[m][f] = abuf[u][m][f];
+        }
+      load_x(abuf[u], d + u);
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+        int4v r[F::LOADS];
+#pragma unroll
+        for (int h = 0; h < F::LOADS; h++) r[h] = rbuf[t][u][h];
+        const Aux ax = auxbuf[t][u];
+        load_w(rbuf[t][u], auxbuf[t][u], t, d + u);
+        consume(x, r, ax, acc[t]);
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; u++)
+#pragma unroll
+    for (int t = 0; t < NT; t++)
+      consume(abuf[u], rbuf[t][u], auxbuf[t][u], acc[t]);
+
+  // Cross-wave reduction in wave order, one live m-tile at a time.
+  __shared__ f32x4 red[WPB > 1 ? (WPB - 1) * NT * 64 : 1];
+  if (WPB > 1) {
+#pragma unroll
+    for (int m = 0; m < MT; m++) {
+      if (!live(m)) break;
+      if (m > 0) __syncthreads();
+      if (wid > 0) {
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+          red[((wid - 1) * NT + t) * 64 + lane] = acc[t][m];
+      }
+      __syncthreads();
+      if (wid == 0) {
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+          for (int r = 0; r < WPB - 1; r++) {
+            f32x4 o = red[(r * NT + t) * 64 + lane];
+            acc[t][m].x += o.x; acc[t][m].y += o.y;
+            acc[t][m].z += o.z; acc[t][m].w += o.w;
+          }
+      }
+    }
+    if (wid > 0) return;
+  }
+
+  // The row scales of this lane's columns (fp8), gate tiles then up tiles.
+  float sc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    sc[t] = 1.f;
+    if constexpr (F::SCALED) {
+      int col = n0 + (t % NTO) * 16 + lr;
+      col = col < NO ? col : NO - 1;
+      if (kGlu && t >= NTO) col += NO;
+      sc[t] = scale[erow + col];
+    }
+  }
+  // C layout: lane holds chunk row 16 m + lg*4 + i, column tilecol + lr.
+#pragma unroll
+  for (int m = 0; m < MT; m++)
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int r = m * 16 + lg * 4 + i;
+      if (r >= cnt) continue;
+      if constexpr (EPI == WEIGHTED) {
+        const int p = pair_of[s + r];
+        const float wt = topw[p];
+        float* part = reinterpret_cast<float*>(out) + (size_t)p * N;
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+          const int col = n0 + t * 16 + lr;
+          if (col < N) part[col] = acc[t][m][i] * sc[t] * wt;
+        }
+      } else {
+        short* y = reinterpret_cast<short*>(out) + (size_t)(s + r) * NO;
+#pragma unroll
+        for (int t = 0; t < NTO; t++) {
+          const int col = n0 + t * 16 + lr;
+          if (col >= NO) continue;
+          if constexpr (kGlu)
+            y[col] = silu_mul_bf16(
+                f32_to_bf16(acc[t][m][i] * sc[t]),
+                f32_to_bf16(acc[t + NTO][m][i] * sc[t + NTO]));
+          else
+            y[col] = f32_to_bf16(acc[t][m][i] * sc[t]);
+        }
+      }
+    }
+}
+
+// The (WPB, U, NT) points of the quantised routed GEMM, each at MT = 1, 2 and
+// the three epilogues; U counts steps of F::KSTEP k (128 fp8, 256 mxfp4), NT
+// is even, and (1, 1, 2) accepts every K % F::KSTEP == 0. None uses scratch
+// memory (profiles/README.md, "Routed MoE decode"); mxfp4 (8, 1, 4) would,
+// 224 B per lane at MT = 2, and is not built.
+#define MOE_DECODE_FP8_CONFIGS(X)                                           \
+  X(1, 1, 2) X(1, 2, 2) X(2, 1, 4) X(2, 2, 2) X(4, 1, 2) X(4, 2, 2)          \
+  X(4, 1, 4) X(8, 1, 2)
+#define MOE_DECODE_MXFP4_CONFIGS(X)                                         \
+  X(1, 1, 2) X(1, 2, 2) X(2, 1, 2) X(2, 1, 4) X(4, 1, 2) X(4, 1, 4)          \
+  X(8, 1, 2)
+
 // The (WPB, U, NT) points the binding can launch, each at MT = 1..4 and the
 // three epilogues; U counts 64-k steps, NT is even so that every point has a
 // GLU form, and (1, 1, 2) accepts every K % 64 == 0. None uses scratch
@@ -378,6 +643,125 @@ void dispatch(const RoutedArgs& r, int64_t wpb, int64_t u, int64_t nt) {
 
 bool i32_vec(const torch::Tensor& t) {
   return t.is_cuda() && t.dtype() == torch::kInt32 && t.is_contiguous();
+}
+
+struct QuantArgs {
+  RoutedArgs r;         // r.w unused
+  const void* wq;
+  const void* scale;
+};
+
+// Launches <F, WPB, U, NT, EPI>: one 16-row tile and one chunk for T <= 16,
+// else 32-row chunks on grid.z (distinct experts per token bound every
+// segment by T rows).
+template <class F, int WPB, int U, int NT, int EPI>
+void launch_q(const QuantArgs& q) {
+  const RoutedArgs& r = q.r;
+  const int NO = EPI == moe_decode::GLU ? r.N / 2 : r.N;
+  constexpr int cols = (EPI == moe_decode::GLU ? NT / 2 : NT) * 16;
+  const unsigned gx = (NO + cols - 1) / cols;
+  const auto* wq = static_cast<const typename F::welem*>(q.wq);
+  const auto* sc = static_cast<const typename F::scale_t*>(q.scale);
+  auto stream = at::cuda::getCurrentHIPStream();
+  if (r.T <= 16)
+    moe_decode::moe_skinny_gemm_q_kernel<F, WPB, U, NT, 1, EPI>
+        <<<dim3(gx, r.E, 1), WPB * 64, 0, stream>>>(
+            r.a, wq, sc, r.seg_start, r.pair_of, r.topw, r.out, r.N, r.K,
+            r.topk, r.gather);
+  else
+    moe_decode::moe_skinny_gemm_q_kernel<F, WPB, U, NT, 2, EPI>
+        <<<dim3(gx, r.E, (r.T + 31) / 32), WPB * 64, 0, stream>>>(
+            r.a, wq, sc, r.seg_start, r.pair_of, r.topw, r.out, r.N, r.K,
+            r.topk, r.gather);
+}
+
+template <class F, int EPI>
+void dispatch_q(const char* name, const QuantArgs& q, int64_t wpb, int64_t u,
+                int64_t nt) {
+#define MOE_CASE(WPB, U, NT)                                                 \
+  if (wpb == WPB && u == U && nt == NT) return launch_q<F, WPB, U, NT, EPI>(q);
+  if constexpr (std::is_same<F, skinny::Fp8Coal>::value) {
+    MOE_DECODE_FP8_CONFIGS(MOE_CASE)
+  } else {
+    MOE_DECODE_MXFP4_CONFIGS(MOE_CASE)
+  }
+#undef MOE_CASE
+  TORCH_CHECK(false, name, ": no kernel for (WPB, U, NT) = (", wpb, ", ", u,
+              ", ", nt, ")");
+}
+
+// The checks and the launch of moe_routed_gemm_fp8 / _mxfp4; the callers have
+// checked the dtypes of wq and scale.
+template <class F>
+void routed_quant(const char* name, torch::Tensor out, torch::Tensor a,
+                  torch::Tensor wq, torch::Tensor scale,
+                  torch::Tensor seg_start, torch::Tensor pair_of,
+                  c10::optional<torch::Tensor> topw, int64_t topk, bool gather,
+                  int64_t epilogue, int64_t wpb, int64_t u, int64_t nt) {
+  TORCH_CHECK(epilogue >= 0 && epilogue <= 2, name, ": bad epilogue");
+  const bool glu = epilogue == moe_decode::GLU;
+  const bool weighted = epilogue == moe_decode::WEIGHTED;
+  TORCH_CHECK(a.is_cuda() && wq.is_cuda() && scale.is_cuda() && out.is_cuda() &&
+                  i32_vec(seg_start) && i32_vec(pair_of),
+              name, ": tensors must be on the GPU, seg_start and pair_of "
+              "contiguous int32");
+  TORCH_CHECK(a.dtype() == torch::kBFloat16 &&
+                  out.dtype() == (weighted ? torch::kFloat32
+                                           : torch::kBFloat16),
+              name, ": a bf16, out bf16 (fp32 if weighted)");
+  TORCH_CHECK(a.dim() == 2 && wq.dim() == 3 && out.dim() == 2 &&
+                  scale.dim() == (F::BLOCK_SCALED ? 3 : 2) &&
+                  seg_start.dim() == 1 && pair_of.dim() == 1,
+              name, ": a [rows, K], codes [E, N, K / ", F::WPACK,
+              "], scale [E, N", F::BLOCK_SCALED ? ", K / 32]" : "]",
+              ", out [P, cols]");
+  TORCH_CHECK(a.is_contiguous() && wq.is_contiguous() &&
+                  scale.is_contiguous() && out.is_contiguous(),
+              name, ": tensors must be contiguous");
+  const int64_t P = pair_of.size(0), E = wq.size(0), N = wq.size(1),
+                K = wq.size(2) * F::WPACK;
+  TORCH_CHECK(topk >= 1 && topk <= moe_decode::MAX_TOPK && P >= 1 &&
+                  P % topk == 0 && P / topk <= moe_decode::MAX_T && E >= 1 &&
+                  E <= moe_decode::MAX_E && seg_start.size(0) == E + 1,
+              name, ": needs T <= 64, topk <= 8, E <= 64 and seg_start "
+              "[E + 1]");
+  const int64_t T = P / topk;
+  TORCH_CHECK(a.size(1) == K && a.size(0) == (gather ? T : P) &&
+                  out.size(0) == P && out.size(1) == (glu ? N / 2 : N) &&
+                  scale.size(0) == E && scale.size(1) == N &&
+                  (!F::BLOCK_SCALED || scale.size(2) * 32 == K),
+              name, ": shape mismatch");
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && N < (1 << 27) && (!glu || N % 32 == 0),
+              name, ": needs N % 16 == 0 (N % 32 for the SwiGLU form), got ",
+              N);
+  TORCH_CHECK(wpb > 0 && u > 0 && nt > 0, name, ": bad configuration");
+  const int64_t kstep = wpb * F::KSTEP * u;
+  TORCH_CHECK(K >= kstep && K < (1 << 30) && K % kstep == 0, name,
+              ": needs K % ", kstep, " == 0, got ", K);
+  TORCH_CHECK((uintptr_t)a.data_ptr() % 16 == 0 &&
+                  (uintptr_t)wq.data_ptr() % 16 == 0 &&
+                  (!F::BLOCK_SCALED || (uintptr_t)scale.data_ptr() % 8 == 0),
+              name, ": a and the codes must be 16 B aligned, block scales "
+              "8 B");
+  const float* tw = nullptr;
+  if (weighted) {
+    TORCH_CHECK(topw.has_value() && topw->is_cuda() &&
+                    topw->dtype() == torch::kFloat32 &&
+                    topw->is_contiguous() && topw->numel() == P,
+                name, ": the weighted form needs topw fp32 with T topk "
+                "elements");
+    tw = (const float*)topw->data_ptr();
+  }
+  const QuantArgs q{{(const short*)a.data_ptr(), nullptr,
+                     (const int*)seg_start.data_ptr(),
+                     (const int*)pair_of.data_ptr(), tw, out.data_ptr(),
+                     (int)T, (int)E, (int)N, (int)K, (int)topk,
+                     gather ? 1 : 0},
+                    wq.data_ptr(), scale.data_ptr()};
+  if (glu) dispatch_q<F, moe_decode::GLU>(name, q, wpb, u, nt);
+  else if (weighted) dispatch_q<F, moe_decode::WEIGHTED>(name, q, wpb, u, nt);
+  else dispatch_q<F, moe_decode::PLAIN>(name, q, wpb, u, nt);
+  HIP_CHECK_KERNEL();
 }
 
 }  // namespace
@@ -470,6 +854,37 @@ void moe_routed_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
   HIP_CHECK_KERNEL();
 }
 
+// moe_routed_gemm for W8A16 experts: wq float8_e4m3fn [E, N, K], scale fp32
+// [E, N]; (wpb, u, nt) a point of MOE_DECODE_FP8_CONFIGS, K % (wpb 128 u) == 0.
+void moe_routed_gemm_fp8(torch::Tensor out, torch::Tensor a, torch::Tensor wq,
+                         torch::Tensor scale, torch::Tensor seg_start,
+                         torch::Tensor pair_of,
+                         c10::optional<torch::Tensor> topw, int64_t topk,
+                         bool gather, int64_t epilogue, int64_t wpb, int64_t u,
+                         int64_t nt) {
+  const char* name = "moe_routed_gemm_fp8";
+  TORCH_CHECK(wq.dtype() == at::kFloat8_e4m3fn &&
+                  scale.dtype() == torch::kFloat32,
+              name, ": wq must be float8_e4m3fn, scale fp32");
+  routed_quant<skinny::Fp8Coal>(name, out, a, wq, scale, seg_start, pair_of,
+                                topw, topk, gather, epilogue, wpb, u, nt);
+}
+
+// moe_routed_gemm for W4A16 experts: q uint8 [E, N, K / 2], scale uint8 (e8m0)
+// [E, N, K / 32]; a point of MOE_DECODE_MXFP4_CONFIGS, K % (wpb 256 u) == 0.
+void moe_routed_gemm_mxfp4(torch::Tensor out, torch::Tensor a, torch::Tensor q,
+                           torch::Tensor scale, torch::Tensor seg_start,
+                           torch::Tensor pair_of,
+                           c10::optional<torch::Tensor> topw, int64_t topk,
+                           bool gather, int64_t epilogue, int64_t wpb,
+                           int64_t u, int64_t nt) {
+  const char* name = "moe_routed_gemm_mxfp4";
+  TORCH_CHECK(q.dtype() == torch::kUInt8 && scale.dtype() == torch::kUInt8,
+              name, ": q and scale must be uint8");
+  routed_quant<skinny::Mxfp4Coal>(name, out, a, q, scale, seg_start, pair_of,
+                                  topw, topk, gather, epilogue, wpb, u, nt);
+}
+
 // out [T, D] bf16 = sum over the topk rows of part [T topk, D] fp32.
 void moe_combine(torch::Tensor out, torch::Tensor part, int64_t topk) {
   TORCH_CHECK(out.is_cuda() && part.is_cuda() &&
@@ -498,5 +913,12 @@ void moe_combine(torch::Tensor out, torch::Tensor part, int64_t topk) {
 std::vector<std::tuple<int, int, int>> moe_decode_configs() {
 #define MOE_ENTRY(WPB, U, NT) {WPB, U, NT},
   return {MOE_DECODE_CONFIGS(MOE_ENTRY)};
+}
+
+// The same per quantised format: {"fp8": [...], "mxfp4": [...]}.
+std::map<std::string, std::vector<std::tuple<int, int, int>>>
+moe_decode_quant_configs() {
+  return {{"fp8", {MOE_DECODE_FP8_CONFIGS(MOE_ENTRY)}},
+          {"mxfp4", {MOE_DECODE_MXFP4_CONFIGS(MOE_ENTRY)}}};
 #undef MOE_ENTRY
 }

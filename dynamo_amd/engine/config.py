@@ -145,8 +145,9 @@ class EngineConfig:
     # decode step, and the freed HBM goes to the KV pool); "mxfp4" stores
     # OCP microscaling FP4, e2m1 codes with one e8m0 scale per 32 k (W4A16:
     # 4.25 bits per weight; every projection K must be a multiple of 32);
-    # "auto" follows DYNAMO_WEIGHT_DTYPE, whose default is bf16. llama/qwen2
-    # only.
+    # "auto" follows DYNAMO_WEIGHT_DTYPE, whose default is bf16. llama/qwen2,
+    # and mixtral on a GPU engine (attention projections and the experts; not
+    # with moe_ep).
     weight_dtype: str = "auto"          # auto | bf16 | fp8 | mxfp4
     # Per-request LoRA: max_loras > 0 allocates an adapter bank of that many
     # slots (each up to max_lora_rank, a multiple of 8; fused PEFT block

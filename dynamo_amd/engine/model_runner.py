@@ -30,12 +30,46 @@ class ModelRunner:
         self.weight_dtype = cfg.resolved_weight_dtype
         if self.weight_dtype in ("fp8", "mxfp4"):
             wd = self.weight_dtype
-            if m.arch in ("opt", "mixtral"):
+            if m.arch == "opt":
                 raise ValueError(
                     f"{wd} weights are not supported for arch {m.arch!r}: "
-                    "only the llama/qwen2 dense projections have a "
-                    "weight-only quantised path (MoE experts and OPT layers "
+                    "only the llama/qwen2 dense projections and the Mixtral "
+                    "experts have a weight-only quantised path (OPT layers "
                     "use other kernels)")
+            if m.arch == "mixtral" and self.device.type != "cuda":
+                raise ValueError(
+                    f"{wd} weights for arch 'mixtral' need a GPU engine: the "
+                    "quantised experts' decode route is the routed HIP "
+                    "kernels of csrc/moe_decode.hip, and a CPU engine would "
+                    "only ever run the per-expert torch loop")
+            if m.arch == "mixtral" and m.moe_ep:
+                raise ValueError(
+                    f"{wd} weights cannot be combined with moe_ep: the "
+                    "expert-parallel route slices bf16 expert tensors on the "
+                    "host")
+            if (m.arch == "mixtral" and cfg.max_num_seqs > ops.MOE_DECODE_MAX_T
+                    and cfg.enable_hip_graphs):
+                raise ValueError(
+                    f"{wd} Mixtral experts decode through the routed kernels "
+                    f"up to {ops.MOE_DECODE_MAX_T} tokens; a larger batch "
+                    "takes the host-side expert loop, which cannot be "
+                    f"captured: max_num_seqs = {cfg.max_num_seqs} needs "
+                    "hipGraphs off")
+            if m.arch == "mixtral" and cfg.enable_hip_graphs:
+                # the same for an expert shape the format's kernel does not
+                # take: every decode step would be the host loop
+                D, I = m.hidden_size, m.intermediate_size // self.tp.size
+                if not (ops.moe_decode_config(2 * I, D, 1, wd) and I % 16 == 0
+                        and ops.moe_decode_config(D, I, 1, wd)
+                        and m.num_experts <= ops.MOE_DECODE_MAX_E
+                        and m.num_experts_per_tok <= ops.MOE_DECODE_MAX_TOPK):
+                    raise ValueError(
+                        f"{wd} weights: the routed MoE decode kernels do not "
+                        f"take this model's experts (hidden {D}, local "
+                        f"intermediate {I}, {m.num_experts} experts, top-"
+                        f"{m.num_experts_per_tok}), so decode would take the "
+                        "host-side expert loop, which cannot be captured: "
+                        "needs hipGraphs off")
             if weight_pool is not None:
                 raise ValueError(
                     f"{wd} weights cannot be combined with a GMS weight pool: "

@@ -75,17 +75,23 @@ class MoEMLP(torch.nn.Module):
         T, D = x.shape
         logits = linear(x, self.router).float()            # [T, E]
         topw, topi = ops.topk_gating(logits, self.topk)    # [T, k]
+        # fp8 / mxfp4 experts (ops.Fp8ExpertWeight, ops.Mxfp4ExpertWeight)
+        quant = not isinstance(self.w_gate_up, torch.Tensor)
         if (x.is_cuda and not self.ep
-                and envs.get("DYNAMO_MOE_FUSED", False, bool)
+                and (quant or envs.get("DYNAMO_MOE_FUSED", False, bool))
                 and ops.moe_decode_ready(x, self.topk, self.w_gate_up,
                                          self.w_down)):
-            # opt-in routed decode (csrc/moe_decode.hip): route, gate/up
-            # GEMM + SwiGLU, weighted down GEMM, combine. Only live experts'
+            # routed decode (csrc/moe_decode.hip): route, gate/up GEMM +
+            # SwiGLU, weighted down GEMM, combine. Only live experts'
             # weights are read; device-side and static, so hipGraph-safe.
+            # Opt-in for bf16 experts, the only decode route of quantised
+            # ones.
             out = ops.moe_decode_mlp(x, topw, topi, self.w_gate_up,
                                      self.w_down)
             return self.tp.all_reduce(out)
         topw = topw.to(x.dtype)
+        if quant:
+            return self.tp.all_reduce(self._expert_loop(x, topw, topi))
 
         out = torch.zeros_like(x)
         flat_expert = topi.reshape(-1).long()              # [T*k]
@@ -173,6 +179,34 @@ class MoEMLP(torch.nn.Module):
         w = topw.reshape(-1)[order].unsqueeze(-1)
         out.index_add_(0, seg_token, (yg * w).to(x.dtype))
         return self.tp.all_reduce(out)
+
+
+    def _expert_loop(self, x, topw, topi):
+        """Every call with quantised experts that the routed kernels do not
+        take (T > 64, a shape outside them, the CPU): the host-side loop over
+        the live experts. holder[e] is expert e's 2-D holder, so ops.linear
+        runs the dense W8A16 / W4A16 kernel on a small segment and
+        dequantise-into-scratch + the library GEMM on a large one; codes
+        never reach torch.bmm or the bf16 grouped kernels. Reads the segment
+        sizes on the host, so it is not graph-capturable."""
+        T = x.shape[0]
+        flat_expert = topi.reshape(-1).long()
+        order = torch.argsort(flat_expert, stable=True)
+        seg_token = (torch.arange(T, device=x.device)
+                     .repeat_interleave(self.topk))[order]
+        counts = torch.bincount(flat_expert, minlength=self.E).tolist()
+        xg = x[seg_token]
+        yg = torch.empty_like(xg)
+        s = 0
+        for e, n in enumerate(counts):
+            if n:
+                gu = linear(xg[s:s + n], self.w_gate_up[e])
+                yg[s:s + n] = linear(ops.silu_mul(gu), self.w_down[e])
+                s += n
+        w = topw.reshape(-1)[order].unsqueeze(-1)
+        out = torch.zeros_like(x)
+        out.index_add_(0, seg_token, (yg * w).to(x.dtype))
+        return out
 
 
 class MixtralDecoderLayer(torch.nn.Module):

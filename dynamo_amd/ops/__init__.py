@@ -9,10 +9,10 @@ from __future__ import annotations
 import torch
 
 from . import fp8_weights, mxfp4_weights, torch_ref
-from .fp8_weights import (Fp8Weight, quantize_fp8_rowwise,  # re-export
-                          quantize_model_fp8)
-from .mxfp4_weights import (Mxfp4Weight, quantize_mxfp4,  # re-export
-                            quantize_model_mxfp4)
+from .fp8_weights import (Fp8ExpertWeight, Fp8Weight,  # re-export
+                          quantize_fp8_rowwise, quantize_model_fp8)
+from .mxfp4_weights import (Mxfp4ExpertWeight, Mxfp4Weight,  # re-export
+                            quantize_mxfp4, quantize_model_mxfp4)
 from .torch_ref import make_cos_sin_cache  # re-export
 
 _hip_mod = None
@@ -615,10 +615,11 @@ def moe_grouped_gemm_seg(x, w, seg_start, max_tokens):
 
 # --------------------------------------------------------------------------
 # Routed MoE decode (csrc/moe_decode.hip): T <= 64 tokens, top-k <= 8 of
-# E <= 64 experts, bf16 expert weights. Route, expert-grouped gate/up GEMM with
-# SwiGLU in its epilogue, expert-grouped down GEMM weighted by the gate
-# weights, per-token combine: four launches, and only live experts' weights
-# are read. Opt-in through DYNAMO_MOE_FUSED=1 (models/mixtral.py).
+# E <= 64 experts, bf16, fp8 or mxfp4 expert weights. Route, expert-grouped
+# gate/up GEMM with SwiGLU in its epilogue, expert-grouped down GEMM weighted
+# by the gate weights, per-token combine: four launches, and only live
+# experts' weights are read. For bf16 experts opt-in through
+# DYNAMO_MOE_FUSED=1 (models/mixtral.py); quantised experts always take it.
 MOE_DECODE_MAX_T, MOE_DECODE_MAX_TOPK, MOE_DECODE_MAX_E = 64, 8, 64
 # (WPB, U, NT) points of moe_routed_gemm; it needs K % (WPB * 64 * U) == 0.
 # A copy of the kernel file's MOE_DECODE_CONFIGS that tests can read without
@@ -643,18 +644,72 @@ MOE_DECODE_SHAPES: dict = {
 }
 
 
-def moe_decode_config(N: int, K: int, T: int):
-    """The (WPB, U, NT) the routed GEMM runs an expert weight [N, K] at for T
-    tokens: the shape's MOE_DECODE_SHAPES entry, else the deepest point of the
-    table (largest K step WPB * 64 * U, the earlier one among equals) that
-    divides K. None if the kernel does not take the shape."""
+# Quantised experts (Fp8ExpertWeight, Mxfp4ExpertWeight): the points of
+# moe_routed_gemm_fp8 / moe_routed_gemm_mxfp4, whose steps are 128 / 256 k;
+# copies of MOE_DECODE_FP8_CONFIGS / MOE_DECODE_MXFP4_CONFIGS of the kernel
+# file, checked against hip().moe_decode_quant_configs(). The routed kernels
+# are these holders' only decode route, so DYNAMO_MOE_FUSED does not apply.
+MOE_DECODE_FP8_CONFIGS: tuple = (
+    (1, 1, 2), (1, 2, 2), (2, 1, 4), (2, 2, 2), (4, 1, 2), (4, 2, 2),
+    (4, 1, 4), (8, 1, 2),
+)
+MOE_DECODE_MXFP4_CONFIGS: tuple = (
+    (1, 1, 2), (1, 2, 2), (2, 1, 2), (2, 1, 4), (4, 1, 2), (4, 1, 4),
+    (8, 1, 2),
+)
+# As MOE_DECODE_SHAPES, per format (`kernel_bench.py --which
+# moe_decode_sweep`; profiles/README.md, "Routed MoE decode"); a shape not
+# listed takes the fallback rule of moe_decode_config.
+MOE_DECODE_FP8_SHAPES: dict = {
+    (28672, 4096): ((4, 2, 2), (2, 1, 4)),    # gate/up
+    (14336, 4096): ((4, 2, 2), (2, 1, 4)),    # gate/up, TP 2
+    (7168, 4096): ((8, 1, 2), (2, 1, 4)),     # gate/up, TP 4
+    (3584, 4096): ((2, 2, 2), (4, 1, 4)),     # gate/up, TP 8
+    (4096, 14336): ((4, 2, 2), (4, 1, 4)),    # down
+    (4096, 7168): ((8, 1, 2), (4, 1, 4)),     # down, TP 2
+    (4096, 3584): ((4, 1, 2), (4, 1, 4)),     # down, TP 4
+    (4096, 1792): ((1, 2, 2), (1, 2, 2)),     # down, TP 8
+}
+MOE_DECODE_MXFP4_SHAPES: dict = {
+    (28672, 4096): ((1, 2, 2), (1, 1, 2)),    # gate/up
+    (14336, 4096): ((4, 1, 4), (2, 1, 4)),    # gate/up, TP 2
+    (7168, 4096): ((4, 1, 4), (1, 1, 2)),     # gate/up, TP 4
+    (3584, 4096): ((1, 2, 2), (2, 1, 4)),     # gate/up, TP 8
+    (4096, 14336): ((8, 1, 2), (4, 1, 4)),    # down
+    (4096, 7168): ((4, 1, 4), (2, 1, 4)),     # down, TP 2
+    (4096, 3584): ((1, 2, 2), (2, 1, 4)),     # down, TP 4
+    (4096, 1792): ((1, 1, 2), (1, 1, 2)),     # down, TP 8
+}
+# format -> (k per step, points, shape table)
+MOE_DECODE_FORMATS: dict = {
+    "bf16": (64, MOE_DECODE_CONFIGS, MOE_DECODE_SHAPES),
+    "fp8": (128, MOE_DECODE_FP8_CONFIGS, MOE_DECODE_FP8_SHAPES),
+    "mxfp4": (256, MOE_DECODE_MXFP4_CONFIGS, MOE_DECODE_MXFP4_SHAPES),
+}
+
+
+def moe_format(w) -> str:
+    """"bf16" | "fp8" | "mxfp4": the routed-GEMM format of expert weights w,
+    a tensor [E, N, K] or an expert holder."""
+    if isinstance(w, Fp8ExpertWeight):
+        return "fp8"
+    return "mxfp4" if isinstance(w, Mxfp4ExpertWeight) else "bf16"
+
+
+def moe_decode_config(N: int, K: int, T: int, fmt: str = "bf16"):
+    """The (WPB, U, NT) the routed GEMM of format `fmt` runs an expert weight
+    [N, K] at for T tokens: the shape's entry in the format's table, else the
+    deepest point of the format's points (largest K step WPB * kstep * U, the
+    earlier one among equals) that divides K. None if the kernel does not
+    take the shape."""
+    kstep, configs, shapes = MOE_DECODE_FORMATS[fmt]
     if not (1 <= T <= MOE_DECODE_MAX_T and N >= 16 and N % 16 == 0
-            and K >= 64 and K % 64 == 0):
+            and K >= kstep and K % kstep == 0):
         return None
-    entry = MOE_DECODE_SHAPES.get((N, K))
+    entry = shapes.get((N, K))
     if entry is not None:
         return entry[0 if T <= 16 else 1]
-    fits = [c for c in MOE_DECODE_CONFIGS if K % (c[0] * 64 * c[1]) == 0]
+    fits = [c for c in configs if K % (c[0] * kstep * c[1]) == 0]
     return max(fits, key=lambda c: c[0] * c[1])
 
 
@@ -672,11 +727,28 @@ def moe_route(topi: torch.Tensor, E: int):
 
 
 def _moe_cfg(w, T, cfg):
-    cfg = cfg or moe_decode_config(w.shape[1], w.shape[2], T)
+    cfg = cfg or moe_decode_config(w.shape[1], w.shape[2], T, moe_format(w))
     if cfg is None:
-        raise ValueError(f"no routed MoE GEMM for expert weights "
-                         f"{tuple(w.shape)} at T = {T}")
+        raise ValueError(f"no routed MoE GEMM for {moe_format(w)} expert "
+                         f"weights {tuple(w.shape)} at T = {T}")
     return cfg
+
+
+def _moe_launch(out, a, w, seg_start, pair_of, topw, topk, gather, epilogue,
+                cfg):
+    """The routed GEMM binding of w's format."""
+    fmt = moe_format(w)
+    if fmt == "bf16":
+        return hip().moe_routed_gemm(out, a, w, seg_start, pair_of, topw,
+                                     topk, gather, epilogue, *cfg)
+    getattr(hip(), "moe_routed_gemm_" + fmt)(
+        out, a, w.q, w.scale, seg_start, pair_of, topw, topk, gather,
+        epilogue, *cfg)
+
+
+def _moe_effective(w, dtype):
+    """Expert weights as a tensor: W_eff of a holder (the CPU path)."""
+    return w if isinstance(w, torch.Tensor) else w.effective(dtype)
 
 
 def moe_routed_gemm(a, w, seg_start, pair_of, topk: int, *, gather: bool,
@@ -684,16 +756,18 @@ def moe_routed_gemm(a, w, seg_start, pair_of, topk: int, *, gather: bool,
     """Sorted row i of expert e times w[e]^T, w [E, N, K] -> bf16 [T topk, N]
     in sorted order. gather: a is x [T, K] and row i is x[pair_of[i] // topk];
     else a is [T topk, K], already sorted. glu: w[e] is a gate/up weight and
-    the result is [T topk, N / 2] = silu_mul of the plain one, equal bits."""
+    the result is [T topk, N / 2] = silu_mul of the plain one, equal bits.
+    w is a bf16 tensor or an Fp8ExpertWeight / Mxfp4ExpertWeight."""
     if not a.is_cuda:
-        return torch_ref.moe_routed_gemm(a, w, seg_start, pair_of, topk,
-                                         gather, glu)
+        return torch_ref.moe_routed_gemm(a, _moe_effective(w, a.dtype),
+                                         seg_start, pair_of, topk, gather,
+                                         glu)
     P = pair_of.numel()
     cfg = _moe_cfg(w, P // topk, cfg)
     y = torch.empty(P, w.shape[1] // 2 if glu else w.shape[1], dtype=a.dtype,
                     device=a.device)
-    hip().moe_routed_gemm(y, a, w, seg_start, pair_of, None, topk, gather,
-                          1 if glu else 0, *cfg)
+    _moe_launch(y, a, w, seg_start, pair_of, None, topk, gather,
+                1 if glu else 0, cfg)
     return y
 
 
@@ -703,40 +777,52 @@ def moe_down_combine(act, w_down, seg_start, pair_of, topw, cfg=None):
     writes fp32 rows already multiplied by the gate weight, the combine sums
     them in ascending j and rounds once."""
     if not act.is_cuda:
-        return torch_ref.moe_down_combine(act, w_down, seg_start, pair_of,
-                                          topw)
+        return torch_ref.moe_down_combine(
+            act, _moe_effective(w_down, act.dtype), seg_start, pair_of, topw)
     T, topk = topw.shape
     cfg = _moe_cfg(w_down, T, cfg)
     part = torch.empty(T * topk, w_down.shape[1], dtype=torch.float32,
                        device=act.device)
-    hip().moe_routed_gemm(part, act, w_down, seg_start, pair_of,
-                          topw.contiguous(), topk, False, 2, *cfg)
+    _moe_launch(part, act, w_down, seg_start, pair_of, topw.contiguous(),
+                topk, False, 2, cfg)
     out = torch.empty(T, w_down.shape[1], dtype=act.dtype, device=act.device)
     hip().moe_combine(out, part, topk)
     return out
 
 
+def _moe_weight_ready(w, fmt: str) -> bool:
+    """What the format's routed GEMM asks of the expert weights' storage."""
+    if fmt == "bf16":
+        return w.dtype == torch.bfloat16 and w.is_contiguous()
+    return (w.q.is_contiguous() and w.scale.is_contiguous()
+            and w.q.data_ptr() % 16 == 0 and w.scale.data_ptr() % 8 == 0)
+
+
 def moe_decode_ready(x, topk: int, w_gate_up, w_down) -> bool:
     """Whether moe_decode_mlp takes the call on the GPU: the kernels' limits
-    on T, top-k and E, bf16, and a configuration for both GEMMs."""
+    on T, top-k and E, bf16 activations, both weights of one format, and a
+    configuration of that format for both GEMMs."""
     T = x.shape[0]
     E, N, K = w_gate_up.shape
+    fmt = moe_format(w_gate_up)
     return (x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16
-            and w_gate_up.dtype == torch.bfloat16
-            and w_down.dtype == torch.bfloat16
+            and moe_format(w_down) == fmt
+            and _moe_weight_ready(w_gate_up, fmt)
+            and _moe_weight_ready(w_down, fmt)
             and 1 <= T <= MOE_DECODE_MAX_T
             and 1 <= topk <= MOE_DECODE_MAX_TOPK and E <= MOE_DECODE_MAX_E
             and N % 32 == 0 and x.is_contiguous()
-            and w_gate_up.is_contiguous() and w_down.is_contiguous()
-            and moe_decode_config(N, K, T) is not None
-            and moe_decode_config(w_down.shape[1], w_down.shape[2], T)
+            and moe_decode_config(N, K, T, fmt) is not None
+            and moe_decode_config(w_down.shape[1], w_down.shape[2], T, fmt)
             is not None)
 
 
 def moe_decode_mlp(x, topw, topi, w_gate_up, w_down):
     """The routed expert MLP of a decode step: x [T, D] bf16, topw / topi
     [T, topk] fp32 / int32 of topk_gating, w_gate_up [E, 2I, D] (gate rows
-    first), w_down [E, D, I] -> [T, D] bf16."""
+    first), w_down [E, D, I] -> [T, D] bf16. The weights are bf16 tensors or
+    expert holders of one format; on the CPU holders compute through
+    torch_ref with effective()."""
     topk = topi.shape[1]
     seg_start, pair_of = moe_route(topi, w_gate_up.shape[0])
     act = moe_routed_gemm(x, w_gate_up, seg_start, pair_of, topk,

@@ -69,6 +69,53 @@ class Fp8Weight:
         return (self.q.float() * self.scale[:, None]).to(dtype)
 
 
+class Fp8ExpertWeight:
+    """Quantised expert weights [E, N, K]: `q` float8_e4m3fn [E, N, K],
+    `scale` fp32 [E, N], the row-wise quantiser applied to every expert's
+    rows. holder[e] is expert e's Fp8Weight over views of both, so ops.linear
+    and fp8_dequant serve a single expert. Not a tensor, as Fp8Weight."""
+
+    __slots__ = ("q", "scale")
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
+        assert q.dtype == torch.float8_e4m3fn and q.dim() == 3
+        assert scale.dtype == torch.float32 and scale.shape == q.shape[:2]
+        self.q = q
+        self.scale = scale
+
+    @staticmethod
+    def from_tensor(w: torch.Tensor) -> "Fp8ExpertWeight":
+        """Quantises one expert at a time: the fp32 temporaries are one
+        expert's, not the tensor's."""
+        assert w.dim() == 3, "Fp8ExpertWeight: w [E, N, K]"
+        q = torch.empty(w.shape, dtype=torch.float8_e4m3fn, device=w.device)
+        scale = torch.empty(w.shape[:2], dtype=torch.float32, device=w.device)
+        for e in range(w.shape[0]):
+            q[e], scale[e] = quantize_fp8_rowwise(w[e])
+        return Fp8ExpertWeight(q, scale)
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+    @property
+    def device(self):
+        return self.q.device
+
+    def dim(self) -> int:
+        return 3
+
+    def __len__(self) -> int:
+        return self.q.shape[0]
+
+    def __getitem__(self, e: int) -> Fp8Weight:
+        return Fp8Weight(self.q[e], self.scale[e])
+
+    def effective(self, dtype: torch.dtype) -> torch.Tensor:
+        """W_eff [E, N, K] in the compute dtype."""
+        return (self.q.float() * self.scale[:, :, None]).to(dtype)
+
+
 # One bf16 scratch buffer per device for the dequantise-then-library path.
 # Stream order makes one buffer enough: the GEMM that reads it is queued
 # before the next dequantisation that overwrites it.
@@ -102,24 +149,47 @@ def is_fp8_model(model) -> bool:
     return getattr(model, "weight_dtype", None) == "fp8"
 
 
+def layer_projections(layer, what: str):
+    """[(module, attribute, dim)] of the weights a quantiser replaces in one
+    layer: the four dense projections (dim 2), or for a MoE layer attn.wqkv /
+    wo and the expert tensors moe.w_gate_up / w_down (dim 3, [E, N, K]); the
+    router stays in the compute dtype. ValueError (`what` names the format)
+    if a weight is missing or is no tensor of that rank."""
+    moe = getattr(layer, "moe", None)
+    if moe is not None and getattr(moe, "ep", False):
+        raise ValueError(f"{what} weights: expert-parallel MoE layers slice "
+                         "bf16 expert tensors on the host")
+    names = (PROJECTIONS[:2] + (("moe", "w_gate_up", 3), ("moe", "w_down", 3))
+             if moe is not None else PROJECTIONS)
+    out = []
+    for sub, name, *rank in names:
+        mod = getattr(layer, sub, None)
+        w = getattr(mod, name, None) if mod is not None else None
+        dim = rank[0] if rank else 2
+        if not isinstance(w, torch.Tensor) or w.dim() != dim:
+            raise ValueError(f"{what} weights: layer has no dense {sub}.{name}"
+                             f" of rank {dim}")
+        out.append((mod, name, dim))
+    return out
+
+
 def quantize_model_fp8(model) -> int:
     """Replace Attention.wqkv / wo and SwiGLUMLP.w_gate_up / w_down of every
-    layer by Fp8Weight holders, layer by layer, freeing each bf16 tensor as it
-    goes. Rank-local: a TP shard quantises its own rows or columns.
-    Embedding, lm_head, norms and biases keep the compute dtype. Returns the
-    number of quantised matrices."""
+    layer by Fp8Weight holders, and a MoE layer's expert tensors by
+    Fp8ExpertWeight holders (one expert at a time), layer by layer, freeing
+    each bf16 tensor as it goes. Rank-local: a TP shard quantises its own rows
+    or columns. Embedding, lm_head, the router, norms and biases keep the
+    compute dtype. Returns the number of quantised tensors."""
     count, largest, device = 0, 0, None
     with torch.no_grad():
         for layer in model.layers:
-            for sub, name in PROJECTIONS:
-                mod = getattr(layer, sub, None)
-                w = getattr(mod, name, None) if mod is not None else None
-                if not isinstance(w, torch.Tensor):
-                    raise ValueError(
-                        f"fp8 weights: layer has no dense {sub}.{name}")
-                holder = Fp8Weight.from_tensor(w)
+            for mod, name, dim in layer_projections(layer, "fp8"):
+                w = getattr(mod, name)
+                holder = (Fp8Weight if dim == 2
+                          else Fp8ExpertWeight).from_tensor(w)
                 setattr(mod, name, holder)
-                largest = max(largest, w.numel())
+                # the scratch buffer holds one matrix: a single expert's
+                largest = max(largest, w[0].numel() if dim == 3 else w.numel())
                 device = w.device
                 del w
                 count += 1

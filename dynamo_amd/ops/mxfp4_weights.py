@@ -31,7 +31,6 @@ from typing import Tuple
 import torch
 
 from . import fp8_weights
-from .fp8_weights import PROJECTIONS
 
 BLOCK = 32
 E_MIN, E_MAX = -100, 100
@@ -118,37 +117,96 @@ class Mxfp4Weight:
         return dequantize_mxfp4(self.q, self.scale, dtype)
 
 
+class Mxfp4ExpertWeight:
+    """Quantised expert weights [E, N, K]: `q` uint8 [E, N, K/2], `scale`
+    uint8 [E, N, K/32], quantize_mxfp4 applied to every expert's rows.
+    holder[e] is expert e's Mxfp4Weight over views of both, so ops.linear and
+    mxfp4_dequant serve a single expert. Not a tensor, as Mxfp4Weight."""
+
+    __slots__ = ("q", "scale")
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
+        assert q.dtype == torch.uint8 and q.dim() == 3
+        assert q.shape[2] % (BLOCK // 2) == 0
+        assert scale.dtype == torch.uint8
+        assert scale.shape == (*q.shape[:2], q.shape[2] * 2 // BLOCK)
+        self.q = q
+        self.scale = scale
+
+    @staticmethod
+    def from_tensor(w: torch.Tensor) -> "Mxfp4ExpertWeight":
+        """Quantises one expert at a time: the fp32 temporaries are one
+        expert's, not the tensor's."""
+        if w.dim() != 3 or w.shape[2] % BLOCK:
+            raise ValueError(
+                f"Mxfp4ExpertWeight: w must be [E, N, K] with K % {BLOCK} "
+                f"== 0, got {tuple(w.shape)}")
+        E, N, K = w.shape
+        q = torch.empty(E, N, K // 2, dtype=torch.uint8, device=w.device)
+        scale = torch.empty(E, N, K // BLOCK, dtype=torch.uint8,
+                            device=w.device)
+        for e in range(E):
+            q[e], scale[e] = quantize_mxfp4(w[e])
+        return Mxfp4ExpertWeight(q, scale)
+
+    @property
+    def shape(self):
+        """The logical (E, N, K)."""
+        return torch.Size((*self.q.shape[:2], self.q.shape[2] * 2))
+
+    @property
+    def device(self):
+        return self.q.device
+
+    def dim(self) -> int:
+        return 3
+
+    def __len__(self) -> int:
+        return self.q.shape[0]
+
+    def __getitem__(self, e: int) -> Mxfp4Weight:
+        return Mxfp4Weight(self.q[e], self.scale[e])
+
+    def effective(self, dtype: torch.dtype) -> torch.Tensor:
+        """W_eff [E, N, K] in the compute dtype."""
+        E, N, K = self.shape
+        return dequantize_mxfp4(self.q.view(E * N, K // 2),
+                                self.scale.view(E * N, K // BLOCK),
+                                dtype).view(E, N, K)
+
+
 def is_mxfp4_model(model) -> bool:
     return getattr(model, "weight_dtype", None) == "mxfp4"
 
 
 def quantize_model_mxfp4(model) -> int:
     """Replace Attention.wqkv / wo and SwiGLUMLP.w_gate_up / w_down of every
-    layer by Mxfp4Weight holders, layer by layer, freeing each bf16 tensor as
-    it goes. Rank-local: a TP shard quantises its own rows or columns, so
-    blocks never span ranks. Embedding, lm_head, norms and biases keep the
-    compute dtype. Raises ValueError if a projection's K is no multiple of
-    32. Returns the number of quantised matrices."""
+    layer by Mxfp4Weight holders, and a MoE layer's expert tensors by
+    Mxfp4ExpertWeight holders (one expert at a time), layer by layer, freeing
+    each bf16 tensor as it goes. Rank-local: a TP shard quantises its own rows
+    or columns, so blocks never span ranks. Embedding, lm_head, the router,
+    norms and biases keep the compute dtype. Raises ValueError if a
+    projection's K is no multiple of 32. Returns the number of quantised
+    tensors."""
     # refuse before the first matrix is replaced
     for layer in model.layers:
-        for sub, name in PROJECTIONS:
-            w = getattr(getattr(layer, sub, None), name, None)
-            if not isinstance(w, torch.Tensor):
+        for mod, name, _ in fp8_weights.layer_projections(layer, "mxfp4"):
+            K = getattr(mod, name).shape[-1]
+            if K % BLOCK:
                 raise ValueError(
-                    f"mxfp4 weights: layer has no dense {sub}.{name}")
-            if w.shape[1] % BLOCK:
-                raise ValueError(
-                    f"mxfp4 weights: {sub}.{name} has K = {w.shape[1]}, "
+                    f"mxfp4 weights: {name} has K = {K}, "
                     f"not a multiple of the {BLOCK}-element MX block")
     count, largest, device = 0, 0, None
     with torch.no_grad():
         for layer in model.layers:
-            for sub, name in PROJECTIONS:
-                mod = getattr(layer, sub)
+            for mod, name, dim in fp8_weights.layer_projections(layer,
+                                                                "mxfp4"):
                 w = getattr(mod, name)
-                holder = Mxfp4Weight.from_tensor(w)
+                holder = (Mxfp4Weight if dim == 2
+                          else Mxfp4ExpertWeight).from_tensor(w)
                 setattr(mod, name, holder)
-                largest = max(largest, w.numel())
+                # the scratch buffer holds one matrix: a single expert's
+                largest = max(largest, w[0].numel() if dim == 3 else w.numel())
                 device = w.device
                 del w
                 count += 1
