@@ -373,6 +373,74 @@ def _bench_mxfp4_gemm(name, x, ws, y, t_bf16, sweep):
                                             glu))
 
 
+def bench_tile_sweep(Ms=(32, 48, 64, 96, 128, 256, 512), reps=3):
+    """The tiled W8A16 / W4A16 GEMM (csrc/quant_tile_gemm.hip) at every
+    launchable point and both W cache policies on the four llama-3-70b layer
+    shapes, cache-cold as bench_skinny_gemm is (launch i reads copy i % R of
+    W, R * bytes(W) >= 1 GiB), against (1) what the dispatch runs with the
+    tiled kernel switched off - the skinny kernel where it applies, else
+    dequantise + the library GEMM, timed as one unit - and (2) the bf16
+    dispatch. The candidates alternate inside each of `reps` rounds; the
+    figure is the minimum. Bytes/s are of stored W (scales included). Picks
+    ops.*_TILE_GEMM_SHAPES and TILE_GEMM_MIN_M / MAX_M."""
+    from dynamo_amd.utils import enable_tunableop
+    enable_tunableop(tuning=False)
+    ops.set_tile_gemm(False)
+    for name, N, K in (("qkv", 10240, 8192), ("o", 8192, 8192),
+                       ("gateup", 57344, 8192), ("down", 8192, 28672)):
+        R = max(2, -(-(1 << 30) // (N * K * 2)))
+        ws = [torch.randn(N, K, dtype=torch.bfloat16, device="cuda") * 0.02
+              for _ in range(R)]
+        for fmt in ("fp8", "mxfp4"):
+            wbytes = N * K if fmt == "fp8" else N * K // 2 + N * K // 32
+            Rq = max(2, -(-(1 << 30) // wbytes))
+            holder = ops.Fp8Weight if fmt == "fp8" else ops.Mxfp4Weight
+            first = [holder.from_tensor(w) for w in ws]
+            hs = [first[r] if r < R else
+                  holder(first[r % R].q.clone(), first[r % R].scale.clone())
+                  for r in range(Rq)]
+            gemm = getattr(ops.hip(), f"{fmt}_tile_gemm")
+            kstep = ops.TILE_GEMM_KSTEP[fmt]
+            for M in Ms:
+                x = torch.randn(M, K, dtype=torch.bfloat16, device="cuda")
+                y = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
+                i = [0]
+
+                def parent():
+                    i[0] += 1
+                    return ops.linear(x, hs[i[0] % Rq])
+
+                def bf16():
+                    i[0] += 1
+                    return ops.linear(x, ws[i[0] % R])
+
+                def tile(p, nt):
+                    i[0] += 1
+                    h = hs[i[0] % Rq]
+                    gemm(y, x, h.q, h.scale, *p, False, nt)
+
+                path = (ops.fp8_linear_path if fmt == "fp8"
+                        else ops.mxfp4_linear_path)(x, hs[0])
+                cands = {f"parent:{path[0]}": parent, "bf16": bf16}
+                for p in ops.TILE_GEMM_CONFIGS[fmt]:
+                    if K % (p[2] * kstep * p[4]) == 0:
+                        for nt in (1, 0):
+                            cands["tile:" + ",".join(map(str, p)) +
+                                  (":nt" if nt else ":dflt")] = (
+                                lambda p=p, nt=nt: tile(p, nt))
+                ts = {c: [] for c in cands}
+                for _ in range(reps):
+                    for c, fn in cands.items():
+                        ts[c].append(timeit(fn, iters=30, warmup=3))
+                for c, v in ts.items():
+                    t = min(v)
+                    print(f"tile_sweep {fmt} {name} M={M} {c}: {t*1e6:8.1f} us "
+                          f"{wbytes/t/1e12:5.2f} TB/s "
+                          f"{2*M*N*K/t/1e12:7.1f} TF", flush=True)
+            del hs, first
+        del ws
+
+
 def _bench_fused_glu(label, fmt, cfg, y, gemm):
     """The gate/up GEMM with the SwiGLU epilogue against the unfused GEMM
     followed by silu_mul, both cache-cold the same way: gemm(out, r, glu)
@@ -651,6 +719,10 @@ if __name__ == "__main__":
         # every launchable routed-GEMM configuration per Mixtral shape:
         # picks ops.MOE_DECODE_SHAPES
         bench_moe_decode_sweep()
+    if w == "tile_sweep":
+        # every launchable point of the tiled quantised GEMM per shape and M:
+        # picks ops.*_TILE_GEMM_SHAPES, TILE_GEMM_MIN_M and TILE_GEMM_MAX_M
+        bench_tile_sweep()
     if w == "fp8sweep":
         # every launchable W8A16 configuration per shape: picks
         # ops.FP8_GEMM_SHAPES

@@ -79,6 +79,15 @@ void mxfp4_skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor q,
                        int64_t nt, bool nontemporal, bool glu);
 int64_t mxfp4_gemm_max_m();
 void mxfp4_dequant(torch::Tensor out, torch::Tensor q, torch::Tensor scale);
+// quant_tile_gemm.hip
+void fp8_tile_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor wq,
+                   torch::Tensor scale, int64_t bm, int64_t wn, int64_t wk,
+                   int64_t nt, int64_t u, bool glu, int64_t nontemporal);
+void mxfp4_tile_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor q,
+                     torch::Tensor scale, int64_t bm, int64_t wn, int64_t wk,
+                     int64_t nt, int64_t u, bool glu, int64_t nontemporal);
+std::map<std::string, std::vector<std::tuple<int, int, int, int, int>>>
+tile_gemm_configs();
 // lora.hip
 void lora_shrink(torch::Tensor t, torch::Tensor x, torch::Tensor A_bank,
                  torch::Tensor slots, torch::Tensor ranks);
@@ -213,6 +222,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_configs", &skinny_gemm_configs);
   // the same, restricted to the entries that take glu = true
   m.def("skinny_gemm_glu_configs", &skinny_gemm_glu_configs);
+  // The tiled W8A16 / W4A16 GEMM (x staged in LDS): the same products for any
+  // M >= 1 at point (BM, WN, WK, NT, U) of tile_gemm_configs(); raises on
+  // anything the kernel does not handle - dispatch lives in ops.linear.
+  // nontemporal < 0: non-temporal W loads iff the call has one M tile
+  m.def("fp8_tile_gemm", &fp8_tile_gemm, py::arg("y"), py::arg("x"),
+        py::arg("wq"), py::arg("scale"), py::arg("bm") = 64,
+        py::arg("wn") = 4, py::arg("wk") = 1, py::arg("nt") = 2,
+        py::arg("u") = 1, py::arg("glu") = false,
+        py::arg("nontemporal") = -1);
+  m.def("mxfp4_tile_gemm", &mxfp4_tile_gemm, py::arg("y"), py::arg("x"),
+        py::arg("q"), py::arg("scale"), py::arg("bm") = 64,
+        py::arg("wn") = 4, py::arg("wk") = 1, py::arg("nt") = 2,
+        py::arg("u") = 1, py::arg("glu") = false,
+        py::arg("nontemporal") = -1);
+  // {"fp8" | "mxfp4": [(BM, WN, WK, NT, U), ...]} they can launch
+  m.def("tile_gemm_configs", &tile_gemm_configs);
   // batched LoRA: each row i takes the adapter in bank slot slots[i] (a
   // device tensor; < 0 = none), so one captured graph serves any adapter mix.
   // t[i, r] = x[i] . A_bank[s, r] and y[i] += scales[s] * t[i] @ B_bank[s]^T

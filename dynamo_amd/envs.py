@@ -40,6 +40,11 @@ ENV_VARS = {
         "0 = gate/up GEMM and silu_mul as two kernels (default: the in-tree "
         "GEMM applies SwiGLU in its epilogue where ops.fused_glu_config "
         "allows; equal bits either way)",
+    "DYNAMO_QUANT_TILE_GEMM":
+        "1 = fp8 / mxfp4 projection GEMMs above the skinny-M kernel's M run "
+        "on the tiled W8A16 / W4A16 kernel (csrc/quant_tile_gemm.hip, x "
+        "staged in LDS) up to ops.TILE_GEMM_MAX_M instead of dequantising "
+        "the weight for the library GEMM. Default: off",
     "DYNAMO_MAX_LORAS":
         "default of the worker's --max-loras: adapter-bank slots for "
         "per-request LoRA (default 0 = engine-level activation only)",

@@ -143,16 +143,22 @@ def _quant_gemm_config(M, N, K, kstep, max_m, shapes, split_k, default):
     return cfg
 
 
-def _quant_linear_path(x, w, dequant_k, gemm_config):
-    """("kernel", cfg) | ("dequant", None) | ("torch", None) for linear(x, w)
-    with a quantised weight holder w whose dequantise kernel needs
-    K % dequant_k == 0."""
+def _quant_linear_path(x, w, dequant_k, gemm_config, fmt=None):
+    """("kernel", cfg) | ("tile", point) | ("dequant", None) | ("torch", None)
+    for linear(x, w) with a quantised weight holder w whose dequantise kernel
+    needs K % dequant_k == 0. fmt names the format's tiled kernel, asked
+    first where it is switched on (its MIN_M may lie below the skinny
+    kernel's largest M); None: the weight cannot take either kernel."""
     N, K = w.shape
     if not x.is_cuda:
         return "torch", None
     if x.dtype != torch.bfloat16 or K % dequant_k or x.shape[-1] != K:
         return "torch", None
     if x.dim() == 2 and x.is_contiguous() and x.data_ptr() % 16 == 0:
+        if fmt is not None and tile_gemm_enabled():
+            point = tile_gemm_config(fmt, x.shape[0], N, K)
+            if point is not None:
+                return "tile", point
         cfg = gemm_config(x.shape[0], N, K)
         if cfg is not None:
             return "kernel", cfg
@@ -160,12 +166,17 @@ def _quant_linear_path(x, w, dequant_k, gemm_config):
 
 
 def _linear_quant(x, w, path, cfg, gemm: str, dequant: str, glu=False):
-    """linear(x, w) on `path`; gemm and dequant name the format's bindings.
-    glu (kernel path only): the fused SwiGLU form, y = [M, N / 2]."""
-    if path == "kernel":
+    """linear(x, w) on `path`; gemm and dequant name the format's bindings
+    (the tiled kernel's is the skinny one's with "tile" for "skinny").
+    glu (kernel and tile paths only): the fused SwiGLU form, y = [M, N / 2]."""
+    if path in ("kernel", "tile"):
         y = torch.empty(x.shape[0], w.shape[0] // 2 if glu else w.shape[0],
                         dtype=x.dtype, device=x.device)
-        getattr(hip(), gemm)(y, x, w.q, w.scale, *cfg, True, glu)
+        if path == "tile":
+            getattr(hip(), gemm.replace("_skinny_", "_tile_"))(
+                y, x, w.q, w.scale, *cfg, glu)
+        else:
+            getattr(hip(), gemm)(y, x, w.q, w.scale, *cfg, True, glu)
         return y
     if path == "dequant":
         w_eff = fp8_weights.scratch_view(w)
@@ -186,8 +197,9 @@ def fp8_linear_path(x: torch.Tensor, w: Fp8Weight):
     the in-tree W8A16 kernel, ("dequant", None) for fp8_dequant into the
     scratch buffer + the library GEMM, ("torch", None) for F.linear(x, W_eff)
     with W_eff formed by torch (CPU, or a GPU call fp8_dequant cannot
-    serve)."""
-    return _quant_linear_path(x, w, 16, fp8_gemm_config)
+    serve). With the tiled kernel switched on (set_tile_gemm) also
+    ("tile", (BM, WN, WK, NT, U)) for fp8_tile_gemm."""
+    return _quant_linear_path(x, w, 16, fp8_gemm_config, "fp8")
 
 
 def _linear_fp8(x: torch.Tensor, w: Fp8Weight) -> torch.Tensor:
@@ -238,15 +250,101 @@ def mxfp4_linear_path(x: torch.Tensor, w: Mxfp4Weight):
     """Where linear(x, w) runs for an Mxfp4Weight: ("kernel", (WPB, U, NT))
     for the in-tree W4A16 kernel, ("dequant", None) for mxfp4_dequant into
     the scratch buffer + the library GEMM, ("torch", None) for
-    F.linear(x, W_eff) with W_eff formed by torch (CPU, or x not bf16)."""
+    F.linear(x, W_eff) with W_eff formed by torch (CPU, or x not bf16). With
+    the tiled kernel switched on (set_tile_gemm) also
+    ("tile", (BM, WN, WK, NT, U)) for mxfp4_tile_gemm."""
     if w.q.data_ptr() % 16 or w.scale.data_ptr() % 8:
         return _quant_linear_path(x, w, 32, lambda M, N, K: None)
-    return _quant_linear_path(x, w, 32, mxfp4_gemm_config)
+    return _quant_linear_path(x, w, 32, mxfp4_gemm_config, "mxfp4")
 
 
 def _linear_mxfp4(x: torch.Tensor, w: Mxfp4Weight) -> torch.Tensor:
     return _linear_quant(x, w, *mxfp4_linear_path(x, w), "mxfp4_skinny_gemm",
                          "mxfp4_dequant")
+
+
+# --------------------------------------------------------------------------
+# Tiled W8A16 / W4A16 GEMM (csrc/quant_tile_gemm.hip): the same formats above
+# the skinny kernel's M, with x staged once per block in LDS. Opt-in
+# (DYNAMO_QUANT_TILE_GEMM=1 / set_tile_gemm): off, every call runs where it
+# ran before. (BM, WN, WK, NT, U) points the bindings can launch; they need
+# K % (WK * KSTEP * U) == 0. Copies of the kernel file's tables that tests can
+# read without the extension; they check them against
+# hip().tile_gemm_configs(). The first point of a format accepts every
+# K % KSTEP == 0. Every point has a GLU form (even NT).
+FP8_TILE_GEMM_CONFIGS: tuple = (
+    (64, 4, 1, 2, 1), (128, 4, 1, 2, 2), (64, 4, 2, 2, 2),
+    (128, 4, 2, 2, 1), (128, 8, 1, 2, 2), (64, 2, 2, 2, 2), (64, 2, 4, 2, 1),
+)
+MXFP4_TILE_GEMM_CONFIGS: tuple = (
+    (64, 4, 1, 2, 1), (128, 4, 1, 2, 1), (64, 4, 2, 2, 1),
+    (128, 8, 1, 2, 1), (64, 8, 1, 2, 2), (64, 2, 2, 2, 1), (64, 1, 2, 2, 1),
+)
+TILE_GEMM_CONFIGS: dict = {"fp8": FP8_TILE_GEMM_CONFIGS,
+                           "mxfp4": MXFP4_TILE_GEMM_CONFIGS}
+TILE_GEMM_KSTEP: dict = {"fp8": 128, "mxfp4": 256}
+# (N, K) -> ((largest M, point), ...) with M ascending, for the llama-3-70b
+# layer shapes: the cold-sweep winners (kernel_bench.py --which tile_sweep;
+# profiles/README.md, "Tiled quantised GEMM"). A shape outside the table, or a
+# K its point does not divide, takes the format's first point.
+FP8_TILE_GEMM_SHAPES: dict = {
+    (10240, 8192): ((128, (64, 4, 2, 2, 2)), (256, (128, 4, 2, 2, 1))),  # qkv
+    (8192, 8192): ((128, (64, 2, 4, 2, 1)), (256, (64, 4, 2, 2, 2))),    # o
+    (57344, 8192): ((256, (128, 8, 1, 2, 2)),),                     # gate/up
+    (8192, 28672): ((128, (64, 2, 4, 2, 1)), (256, (64, 4, 2, 2, 2))),   # down
+}
+MXFP4_TILE_GEMM_SHAPES: dict = {
+    (10240, 8192): ((64, (64, 2, 2, 2, 1)), (128, (64, 4, 2, 2, 1)),
+                    (256, (64, 8, 1, 2, 2))),                            # qkv
+    (8192, 8192): ((128, (64, 2, 2, 2, 1)), (256, (64, 4, 2, 2, 1))),    # o
+    (57344, 8192): ((64, (64, 8, 1, 2, 2)), (256, (128, 8, 1, 2, 1))),
+    (8192, 28672): ((128, (64, 2, 2, 2, 1)), (256, (64, 4, 2, 2, 1))),   # down
+}
+TILE_GEMM_SHAPES: dict = {"fp8": FP8_TILE_GEMM_SHAPES,
+                          "mxfp4": MXFP4_TILE_GEMM_SHAPES}
+# The M the tiled kernel takes. MIN_M: the skinny kernel's largest M + 1, so
+# that no M from 1 to MAX_M dequantises; not lower, because at the skinny
+# kernel's own M the tiled one was ahead on some shapes only (fp8 qkv and
+# gate/up at M = 48 and 64) and behind on the others. MAX_M: at M = 256 it was
+# ahead of dequantise + library on all four shapes in both sweeps (1.16-2.0x
+# fp8, 1.4-2.5x mxfp4); at M = 512, the next M measured, it was behind on qkv
+# (0.82x fp8, 1.00x mxfp4).
+TILE_GEMM_MIN_M: dict = {"fp8": FP8_GEMM_MAX_M + 1,
+                         "mxfp4": MXFP4_GEMM_MAX_M + 1}
+TILE_GEMM_MAX_M: dict = {"fp8": 256, "mxfp4": 256}
+
+_tile_gemm_override: "bool | None" = None
+
+
+def set_tile_gemm(on: "bool | None") -> None:
+    """In-process override of DYNAMO_QUANT_TILE_GEMM (None = follow the
+    env)."""
+    global _tile_gemm_override
+    _tile_gemm_override = on
+
+
+def tile_gemm_enabled() -> bool:
+    if _tile_gemm_override is not None:
+        return _tile_gemm_override
+    from dynamo_amd import envs
+    return envs.get("DYNAMO_QUANT_TILE_GEMM", False, bool)
+
+
+def tile_gemm_config(fmt: str, M: int, N: int, K: int):
+    """The (BM, WN, WK, NT, U) the tiled kernel of fmt ("fp8" | "mxfp4") runs
+    an [M, K] x [N, K]^T call at, or None if it does not take the call: M
+    outside [TILE_GEMM_MIN_M, TILE_GEMM_MAX_M] or a shape the kernel cannot
+    do. The switch is the caller's business."""
+    kstep = TILE_GEMM_KSTEP[fmt]
+    if not (TILE_GEMM_MIN_M[fmt] <= M <= TILE_GEMM_MAX_M[fmt]
+            and K >= kstep and K % kstep == 0 and N >= 16 and N % 16 == 0):
+        return None
+    point = TILE_GEMM_CONFIGS[fmt][0]
+    for max_m, p in TILE_GEMM_SHAPES[fmt].get((N, K), ()):
+        if M <= max_m and K % (p[2] * kstep * p[4]) == 0:
+            point = p
+            break
+    return point
 
 
 def linear(x: torch.Tensor, w) -> torch.Tensor:
@@ -312,13 +410,14 @@ def fused_glu_config(x: torch.Tensor, w):
     I = N / 2 is a multiple of 16."""
     if not fused_glu_enabled() or w.shape[0] % 32:
         return None
-    if isinstance(w, Fp8Weight):
-        path, cfg = fp8_linear_path(x, w)
-        hit = ("fp8_skinny_gemm", "fp8", cfg) if path == "kernel" else None
-    elif isinstance(w, Mxfp4Weight):
-        path, cfg = mxfp4_linear_path(x, w)
-        hit = (("mxfp4_skinny_gemm", "mxfp4", cfg) if path == "kernel"
-               else None)
+    if isinstance(w, (Fp8Weight, Mxfp4Weight)):
+        fmt = "fp8" if isinstance(w, Fp8Weight) else "mxfp4"
+        path, cfg = (fp8_linear_path if fmt == "fp8"
+                     else mxfp4_linear_path)(x, w)
+        if path == "tile":   # every point of the tiled kernel has a GLU form
+            return ((f"{fmt}_tile_gemm", cfg) if fmt in FUSED_GLU_FORMATS
+                    and cfg[3] % 2 == 0 else None)
+        hit = (f"{fmt}_skinny_gemm", fmt, cfg) if path == "kernel" else None
     else:
         cfg = skinny_gemm_config(x, w)
         hit = None if cfg is None else (
@@ -338,7 +437,8 @@ def linear_silu_mul(x: torch.Tensor, w_gate_up) -> torch.Tensor:
         return silu_mul(linear(x, w_gate_up))
     gemm, cfg = hit
     if gemm != "skinny_gemm":
-        return _linear_quant(x, w_gate_up, "kernel", cfg, gemm, None, True)
+        path = "tile" if gemm.endswith("_tile_gemm") else "kernel"
+        return _linear_quant(x, w_gate_up, path, cfg, gemm, None, True)
     y = torch.empty(x.shape[0], w_gate_up.shape[0] // 2, dtype=x.dtype,
                     device=x.device)
     hip().skinny_gemm(y, x, w_gate_up, *cfg, True)

@@ -26,6 +26,7 @@ hip_sources = [
         "attention_decode.hip",
         "attention_prefill.hip",
         "skinny_gemm.hip",
+        "quant_tile_gemm.hip",
         "sampling.hip",
         "logits_process.hip",
         "moe.hip",
