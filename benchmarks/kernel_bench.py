@@ -70,6 +70,96 @@ def bench_decode_attn(B=16, ctx=8192, Hq=64, Hkv=8, ps=64):
           f"nt {n*1e6:8.1f} us {gb/n:7.2f} GB/s")
 
 
+def bench_mq_attn(S=16, Hkv=8, G=8, ps=64, ctxs=(8192, 2048),
+                  q_lens=(2, 4, 8), rounds=3, window=0.2):
+    """Short query runs on long contexts: ops.paged_attention_multiquery
+    against ops.attention_prefill_paged on the same inputs, and the
+    single-token decode kernel at the same context as the bandwidth
+    yardstick. Cache-cold: call i reads copy i % R of the K/V caches, R
+    copies together past 640 MB (the Infinity Cache holds 256 MB). Device
+    events around >= `window` s of back-to-back eager calls, the three
+    alternated `rounds` times, best of the rounds. The multi-query figure is
+    the whole op: row_ctx construction, phase 1 and the chunk merge."""
+    hd, Hq, dev = 128, Hkv * G, "cuda"
+    scale = hd ** -0.5
+
+    def event_time(fn, n):
+        start, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        start.record()
+        for i in range(n):
+            fn(i)
+        end.record()
+        end.synchronize()
+        return start.elapsed_time(end) * 1e-3 / n
+
+    for fp8 in (False, True):
+        for ctx in ctxs:
+            ppseq = (ctx + ps - 1) // ps
+            kv_bytes = 2 * S * ctx * Hkv * hd * (1 if fp8 else 2)
+            R = max(1, -(-640_000_000 // kv_bytes))
+            store = torch.float8_e4m3fn if fp8 else torch.bfloat16
+            caches = []
+            for _ in range(R):
+                k = torch.randn(S * ppseq, Hkv, ps, hd, dtype=torch.bfloat16,
+                                device=dev)
+                v = torch.randn(S * ppseq, Hkv, hd, ps, dtype=torch.bfloat16,
+                                device=dev)
+                caches.append((k.to(store), v.to(store)))
+            pt = torch.arange(S * ppseq, dtype=torch.int32,
+                              device=dev).view(S, -1)
+            ctxl = torch.full((S,), ctx, dtype=torch.int32, device=dev)
+            dscratch = ops.DecodeScratch(S, Hq, hd, ctx, dev)
+            q1 = torch.randn(S, Hq, hd, dtype=torch.bfloat16, device=dev)
+
+            def decode(i):
+                kc, vc = caches[i % R]
+                ops.paged_attention_decode(q1, kc, vc, pt, ctxl, scale,
+                                           dscratch, v_transposed=True)
+
+            for ql in q_lens:
+                q = torch.randn(S * ql, Hq, hd, dtype=torch.bfloat16,
+                                device=dev)
+                starts = torch.arange(0, S * ql, ql, dtype=torch.int32,
+                                      device=dev)
+                qlen = torch.full((S,), ql, dtype=torch.int32, device=dev)
+                tiles = ops.build_prefill_tiles(
+                    [ql] * S, dev, ops.prefill_tile_rows(Hq, Hkv))
+                scratch = ops.MultiQueryScratch(S * ql, Hq, hd, ctx, dev)
+
+                def mq(i):
+                    kc, vc = caches[i % R]
+                    return ops.paged_attention_multiquery(
+                        q, kc, vc, pt, starts, qlen, ctxl, scale, scratch, ql)
+
+                def prefill(i):
+                    kc, vc = caches[i % R]
+                    return ops.attention_prefill_paged(
+                        q, kc, vc, pt, starts, qlen, ctxl, scale, tiles,
+                        v_transposed=True)
+
+                diff = float((mq(0).float() - prefill(0).float()).abs().max())
+                fns = {"mq": mq, "prefill": prefill, "decode": decode}
+                n = {}
+                for name, fn in fns.items():
+                    event_time(fn, 2 * R)                       # warm-up
+                    n[name] = max(2 * R, int(window / event_time(fn, 2 * R)))
+                ts = {name: [] for name in fns}
+                for _ in range(rounds):
+                    for name, fn in fns.items():
+                        ts[name].append(event_time(fn, n[name]))
+                t = {name: min(v) for name, v in ts.items()}
+                gb = kv_bytes / 1e9
+                print(f"mq_attn {'fp8 ' if fp8 else 'bf16'} S{S} Hq{Hq}/{Hkv} "
+                      f"ctx{ctx} q{ql} R={R}: mq {t['mq']*1e6:7.1f} us "
+                      f"{gb/t['mq']:5.0f} GB/s | prefill "
+                      f"{t['prefill']*1e6:7.1f} us | decode(q1) "
+                      f"{t['decode']*1e6:7.1f} us {gb/t['decode']:5.0f} GB/s | "
+                      f"prefill/mq {t['prefill']/t['mq']:5.2f}x | mq/decode "
+                      f"{t['mq']/t['decode']:4.2f}x | max |mq - prefill| "
+                      f"{diff:.1e}", flush=True)
+            del caches
+
+
 def bench_prefill_attn(S=8192, Hq=32, Hkv=8, ps=64, v_transposed=False):
     hd = 128
     npages = (S + ps - 1) // ps
@@ -692,6 +782,8 @@ if __name__ == "__main__":
         bench_prefill_attn(S=2048)
         bench_prefill_attn(Hq=64)          # GQA 8 (llama-70b TP1)
         bench_prefill_attn(S=2048, Hq=64)
+    if w in ("all", "mq_attn"):
+        bench_mq_attn()
     if w in ("all", "append"):
         bench_kv_append()
     if w in ("all", "sample"):

@@ -38,6 +38,13 @@ void paged_attention_decode(torch::Tensor out, torch::Tensor q, torch::Tensor kc
                             torch::Tensor ml, double scale,
                             int64_t chunk_tokens, bool v_transposed,
                             int64_t nt_policy);
+// attention_multiquery.hip
+void paged_attention_multiquery(
+    torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
+    torch::Tensor vcache, torch::Tensor page_table, torch::Tensor seq_q_start,
+    torch::Tensor seq_q_len, torch::Tensor seq_ctx_len, torch::Tensor row_ctx,
+    torch::Tensor partial, torch::Tensor ml, double scale,
+    int64_t chunk_tokens, int64_t max_q_len);
 // attention_prefill.hip
 void attention_prefill_paged(torch::Tensor out, torch::Tensor q,
                              torch::Tensor kcache, torch::Tensor vcache,
@@ -165,6 +172,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("page_table"), py::arg("ctx_lens"), py::arg("partial"),
         py::arg("ml"), py::arg("scale"), py::arg("chunk_tokens"),
         py::arg("v_transposed") = false, py::arg("nt_policy") = -1);
+  // 2..8 query tokens per sequence on a long context, split over the
+  // context like decode (d-major V pages, hd 128, q_len * G <= 64);
+  // row_ctx[Tq] is the causal limit of every flattened q row
+  m.def("paged_attention_multiquery", &paged_attention_multiquery,
+        py::arg("out"), py::arg("q"), py::arg("kcache"), py::arg("vcache"),
+        py::arg("page_table"), py::arg("seq_q_start"), py::arg("seq_q_len"),
+        py::arg("seq_ctx_len"), py::arg("row_ctx"), py::arg("partial"),
+        py::arg("ml"), py::arg("scale"), py::arg("chunk_tokens"),
+        py::arg("max_q_len"));
   m.def("attention_prefill_paged", &attention_prefill_paged,
         py::arg("out"), py::arg("q"), py::arg("kcache"), py::arg("vcache"),
         py::arg("page_table"), py::arg("tile_seq"), py::arg("tile_q0"),

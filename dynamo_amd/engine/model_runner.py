@@ -124,6 +124,12 @@ class ModelRunner:
             self.decode_scratch = ops.DecodeScratch(
                 cfg.max_num_seqs, self.hq_local, m.head_dim,
                 cfg.max_model_len, self.device)
+        # split-KV multi-query attention for short prefill runs (opt-in)
+        self.multiquery_scratch = None
+        if self.device.type == "cuda" and ops.multiquery_attn_enabled():
+            self.multiquery_scratch = ops.MultiQueryScratch(
+                min(cfg.max_num_seqs * ops.MQ_MAX_Q, cfg.max_batched_tokens),
+                self.hq_local, m.head_dim, cfg.max_model_len, self.device)
 
     def _auto_pages(self) -> int:
         m = self.cfg.model
@@ -244,7 +250,15 @@ class ModelRunner:
             meta.embeds_rows = torch.tensor(embeds_rows, dtype=torch.int64,
                                             device=dev)
             meta.inputs_embeds = torch.cat(embeds_parts, 0).to(dev)
-        if qpos and dev.type == "cuda":
+        mq = self.multiquery_scratch
+        if (qpos and mq is not None and ops.multiquery_attn_enabled()
+                and qpos <= mq.max_rows
+                and ops.multiquery_ready(q_len, self.hq_local, self.hkv_local,
+                                         cfg.model.head_dim, ps,
+                                         self.v_transposed,
+                                         cfg.kv_torch_dtype)):
+            meta.prefill_multiquery = (max(q_len), mq)
+        elif qpos and dev.type == "cuda":
             rows = ops.prefill_tile_rows(self.hq_local, self.hkv_local)
             meta.prefill_tiles = ops.build_prefill_tiles(q_len, dev, rows)
         input_ids = torch.tensor(tokens, dtype=torch.int32).to(dev, non_blocking=True)

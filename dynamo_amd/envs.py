@@ -45,6 +45,12 @@ ENV_VARS = {
         "on the tiled W8A16 / W4A16 kernel (csrc/quant_tile_gemm.hip, x "
         "staged in LDS) up to ops.TILE_GEMM_MAX_M instead of dequantising "
         "the weight for the library GEMM. Default: off",
+    "DYNAMO_MQ_ATTN":
+        "1 = a step whose prefill part is runs of at most ops.MQ_MAX_Q query "
+        "tokens per sequence (q_len * G <= ops.MQ_MAX_COLS, d-major V pages, "
+        "head_dim 128) attends through the split-KV multi-query kernel "
+        "(csrc/attention_multiquery.hip) instead of the prefill kernel. "
+        "Default: off",
     "DYNAMO_MAX_LORAS":
         "default of the worker's --max-loras: adapter-bank slots for "
         "per-request LoRA (default 0 = engine-level activation only)",

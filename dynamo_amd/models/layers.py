@@ -37,6 +37,10 @@ class AttnMetadata:
     seq_q_len: Optional[torch.Tensor] = None
     seq_ctx_len: Optional[torch.Tensor] = None
     prefill_tiles: Optional[tuple] = None
+    # (max_q_len, ops.MultiQueryScratch) when the prefill part is short query
+    # runs that take the split-KV multi-query kernel (opt-in, see
+    # ops.multiquery_ready); prefill_tiles is then not built
+    prefill_multiquery: Optional[tuple] = None
     # sampling
     logits_rows: Optional[torch.Tensor] = None         # [Bs] int64 rows to sample
     # prompt_embeds injection (reference parity: PreprocessedRequest
@@ -244,7 +248,13 @@ class Attention(torch.nn.Module):
                 qh[:nd], kcache, vcache, meta.decode_page_table,
                 meta.decode_ctx_lens, self.scale, meta.decode_scratch,
                 out=out[:nd], v_transposed=meta.v_transposed)
-        if meta.num_prefill_tokens:
+        if meta.num_prefill_tokens and meta.prefill_multiquery is not None:
+            max_q_len, mq_scratch = meta.prefill_multiquery
+            out[nd:] = ops.paged_attention_multiquery(
+                qh[nd:].contiguous(), kcache, vcache, meta.prefill_page_table,
+                meta.seq_q_start, meta.seq_q_len, meta.seq_ctx_len, self.scale,
+                mq_scratch, max_q_len, v_transposed=meta.v_transposed)
+        elif meta.num_prefill_tokens:
             out[nd:] = ops.attention_prefill_paged(
                 qh[nd:].contiguous(), kcache, vcache, meta.prefill_page_table,
                 meta.seq_q_start, meta.seq_q_len, meta.seq_ctx_len, self.scale,

@@ -610,6 +610,98 @@ def attention_prefill_paged(q, kcache, vcache, page_table, seq_q_start,
                                              v_transposed=v_transposed)
 
 
+# --------------------------------------------------------------------------
+# Split-KV multi-query attention (csrc/attention_multiquery.hip): short query
+# runs (a prefix-cache hit's remainder, a chunked prefill's tail, a
+# speculative verification step) on long contexts, streamed like decode with
+# the run folded onto the MFMA columns beside the GQA group. Opt-in
+# (DYNAMO_MQ_ATTN=1 / set_multiquery_attn): off, such steps take the prefill
+# kernel as before.
+MQ_MAX_Q = 8        # query tokens per sequence
+MQ_MAX_COLS = 64    # q_len * G: four 16-column MFMA tiles
+
+_multiquery_override: "bool | None" = None
+
+
+def set_multiquery_attn(on: "bool | None") -> None:
+    """In-process override of DYNAMO_MQ_ATTN (None = follow the env)."""
+    global _multiquery_override
+    _multiquery_override = on
+
+
+def multiquery_attn_enabled() -> bool:
+    if _multiquery_override is not None:
+        return _multiquery_override
+    from dynamo_amd import envs
+    return envs.get("DYNAMO_MQ_ATTN", False, bool)
+
+
+def multiquery_ready(q_lens, Hq: int, Hkv: int, head_dim: int, page_size: int,
+                     v_transposed: bool, kv_dtype) -> bool:
+    """Can the multi-query kernel take a step whose sequences bring q_lens
+    (host ints) new tokens? Host values only: no device sync."""
+    if not q_lens or Hkv <= 0 or Hq % Hkv:
+        return False
+    G = Hq // Hkv
+    longest = max(q_lens)
+    return (v_transposed and 2 <= G <= 16 and head_dim == 128
+            and page_size % 32 == 0 and page_size & (page_size - 1) == 0
+            and kv_dtype in (torch.bfloat16, torch.float8_e4m3fn)
+            and min(q_lens) >= 0 and 1 <= longest <= MQ_MAX_Q
+            and longest * G <= MQ_MAX_COLS)
+
+
+class MultiQueryScratch:
+    """Chunk partials of the multi-query kernel, one row per query token
+    (DecodeScratch's chunk rule)."""
+
+    def __init__(self, max_rows: int, num_q_heads: int, head_dim: int,
+                 max_ctx: int, device):
+        self.chunks = int(hip().paged_decode_num_chunks(max_ctx))
+        self.chunk_tokens = int(hip().decode_chunk_tokens(max_ctx))
+        self.max_rows = max_rows
+        self.partial = torch.empty(max_rows, num_q_heads, self.chunks,
+                                   head_dim, dtype=torch.float32,
+                                   device=device)
+        self.ml = torch.empty(max_rows, num_q_heads, self.chunks, 2,
+                              dtype=torch.float32, device=device)
+
+
+def multiquery_row_ctx(seq_q_start, seq_q_len, seq_ctx_len, Tq: int):
+    """[Tq] int32: the tokens each flattened q row sees, ctx - q_len + j + 1
+    for row j of its run. Stays on the tensors' device, no host sync."""
+    base = (seq_ctx_len - seq_q_len - seq_q_start).to(torch.int32)
+    rows = torch.arange(1, Tq + 1, dtype=torch.int32, device=base.device)
+    return torch.repeat_interleave(base, seq_q_len.long(),
+                                   output_size=Tq) + rows
+
+
+def paged_attention_multiquery(q, kcache, vcache, page_table, seq_q_start,
+                               seq_q_len, seq_ctx_len, scale,
+                               scratch: "MultiQueryScratch | None" = None,
+                               max_q_len: int = MQ_MAX_Q, v_transposed=True):
+    """Causal paged attention of short query runs, q [Tq, Hq, hd] ->
+    [Tq, Hq, hd], with attention_prefill_paged's semantics: row j of a run
+    sits at position ctx - q_len + j. max_q_len is the host's bound on
+    seq_q_len (it picks the kernel's column tiles)."""
+    if q.is_cuda:
+        assert v_transposed, "the multi-query kernel reads d-major V pages"
+        assert scratch is not None, "GPU multi-query needs a MultiQueryScratch"
+        Tq = q.shape[0]
+        assert Tq <= scratch.max_rows, (Tq, scratch.max_rows)
+        out = torch.empty_like(q)
+        row_ctx = multiquery_row_ctx(seq_q_start, seq_q_len, seq_ctx_len, Tq)
+        hip().paged_attention_multiquery(
+            out, q, kcache, vcache, page_table, seq_q_start, seq_q_len,
+            seq_ctx_len, row_ctx, scratch.partial, scratch.ml, scale,
+            scratch.chunk_tokens, max_q_len)
+        return out
+    return torch_ref.attention_prefill_paged(q, kcache, vcache, page_table,
+                                             seq_q_start, seq_q_len,
+                                             seq_ctx_len, scale,
+                                             v_transposed=v_transposed)
+
+
 def greedy_sample(logits: torch.Tensor, allow_fast: bool = True) -> torch.Tensor:
     if logits.is_cuda:
         out = torch.empty(logits.shape[0], dtype=torch.int32,

@@ -24,6 +24,7 @@ hip_sources = [
         "activation.hip",
         "cache.hip",
         "attention_decode.hip",
+        "attention_multiquery.hip",
         "attention_prefill.hip",
         "skinny_gemm.hip",
         "quant_tile_gemm.hip",
