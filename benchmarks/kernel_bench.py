@@ -761,6 +761,95 @@ def bench_moe_decode_sweep(Ts=(1, 16, 64), tps=(1, 2, 4, 8), window=0.15,
             del ws
 
 
+def _eager_time(fn, n):
+    """Seconds per call of fn over n back-to-back eager calls, by device
+    events around synchronised work (fn may read back to the host)."""
+    torch.cuda.synchronize()
+    start, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+    start.record()
+    for _ in range(n):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) * 1e-3 / n
+
+
+def bench_moe_tiled_sweep(Ts=(128, 256, 512, 1024, 2048), tps=(1, 2),
+                          fmts=("fp8", "mxfp4"), rounds=3, window=0.1):
+    """The tiled routed MoE (ops.moe_tiled_mlp: route + gate/up GEMM with
+    SwiGLU + weighted down GEMM + combine) against the host-side expert loop
+    it replaces (MoEMLP._expert_loop), on Mixtral-8x7B's experts and their
+    TP-2 shards, E = 8, top-2 with seeded random routing. Both are warmed up
+    and then alternated `rounds` times eagerly: picks ops.MOE_TILE_MAX_T.
+    Before that, every point of ops.MOE_TILE_CONFIGS at the T's BM on each
+    GEMM alone (captured graphs): picks ops.MOE_TILE_SHAPES."""
+    from dynamo_amd.engine.config import ModelConfig
+    from dynamo_amd.models.layers import TPContext
+    from dynamo_amd.models.mixtral import MoEMLP
+    m = MIXTRAL
+    E, K, D = m["E"], m["topk"], m["D"]
+    holder = {"fp8": ops.Fp8ExpertWeight.from_tensor,
+              "mxfp4": ops.Mxfp4ExpertWeight.from_tensor}
+    for tp in tps:
+        I = m["I"] // tp
+        cfg = ModelConfig(name="mixtral-8x7b-moe", arch="mixtral",
+                          hidden_size=D, intermediate_size=I, num_experts=E,
+                          num_experts_per_tok=K)
+        moe = MoEMLP(cfg, TPContext(), "cuda", torch.bfloat16)
+        w16 = (moe.w_gate_up, moe.w_down)
+        for f in fmts:
+            wgu, wd = (holder[f](w) for w in w16)
+            moe.w_gate_up, moe.w_down = wgu, wd
+            kstep = ops.MOE_DECODE_FORMATS[f][0]
+            t = {}
+            for T in Ts:
+                gen = torch.Generator(device="cuda").manual_seed(T)
+                topw, topi = ops.topk_gating(
+                    torch.randn(T, E, device="cuda", generator=gen), K)
+                x = torch.randn(T, D, dtype=torch.bfloat16, device="cuda",
+                                generator=gen)
+                bm = ops.moe_tile_bm(T, K, E)
+                route = ops.moe_route_tiled(topi, E, bm)
+                act = ops.moe_tiled_gemm(x, wgu, route, K, gather=True,
+                                         glu=True)
+                for name, w in (("gate_up", wgu), ("down", wd)):
+                    fits = [c for c in ops.MOE_TILE_CONFIGS[f] if c[0] == bm
+                            and w.shape[2] % (c[2] * kstep * c[4]) == 0]
+                    for c in fits:
+                        if name == "gate_up":
+                            fn = lambda: ops.moe_tiled_gemm(  # noqa: E731
+                                x, w, route, K, gather=True, glu=True, cfg=c)
+                        else:
+                            fn = lambda: ops.moe_tiled_down_combine(  # noqa: E731
+                                act, w, route, topw, cfg=c)
+                        g = _capture(fn)
+                        t[name, T, c] = _event_time(g, _replays_for(g, window))
+                    print(f"moe_tiled_sweep POINTS {f} {name} "
+                          f"{tuple(w.shape[1:])} T={T:4d} BM={bm}: "
+                          + " | ".join(f"{c[1:]} {t[name, T, c]*1e6:7.1f}"
+                                       for c in fits) + " us; best "
+                          f"{min(fits, key=lambda c: t[name, T, c])[1:]}")
+                tiled = lambda: ops.moe_tiled_mlp(x, topw, topi, wgu, wd)  # noqa: E731
+                loop = lambda: moe._expert_loop(  # noqa: E731
+                    x, topw.to(x.dtype), topi)
+                with torch.no_grad():
+                    diff = float((tiled().float() - loop().float()).abs().max()
+                                 / loop().float().abs().max())
+                    n = {r: max(3, int(window / _eager_time(fn, 3)) + 1)
+                         for r, fn in (("tiled", tiled), ("loop", loop))}
+                    ts = {"tiled": [], "loop": []}
+                    for _ in range(rounds):
+                        ts["tiled"].append(_eager_time(tiled, n["tiled"]))
+                        ts["loop"].append(_eager_time(loop, n["loop"]))
+                print(f"moe_tiled_sweep MLP {f} tp{tp} T={T:4d} BM={bm}: "
+                      + " | ".join(f"{r} {min(v)*1e6:8.1f}-{max(v)*1e6:8.1f} us"
+                                   for r, v in ts.items())
+                      + f" | loop/tiled {min(ts['loop'])/min(ts['tiled']):5.2f}x"
+                      f" | max |tiled - loop| / max |loop| {diff:.1e}")
+            del wgu, wd
+        del moe, w16
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--which", default="all")
@@ -811,6 +900,11 @@ if __name__ == "__main__":
         # every launchable routed-GEMM configuration per Mixtral shape:
         # picks ops.MOE_DECODE_SHAPES
         bench_moe_decode_sweep()
+    if w == "moe_tiled_sweep":
+        # the tiled routed MoE against the host-side expert loop, and every
+        # launchable point per Mixtral shape: picks ops.MOE_TILE_MAX_T and
+        # ops.MOE_TILE_SHAPES
+        bench_moe_tiled_sweep()
     if w == "tile_sweep":
         # every launchable point of the tiled quantised GEMM per shape and M:
         # picks ops.*_TILE_GEMM_SHAPES, TILE_GEMM_MIN_M and TILE_GEMM_MAX_M

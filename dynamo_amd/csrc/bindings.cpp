@@ -131,6 +131,27 @@ void moe_combine(torch::Tensor out, torch::Tensor part, int64_t topk);
 std::vector<std::tuple<int, int, int>> moe_decode_configs();
 std::map<std::string, std::vector<std::tuple<int, int, int>>>
 moe_decode_quant_configs();
+// moe_tile_gemm.hip
+void moe_route_tiled(torch::Tensor topi, torch::Tensor seg_start,
+                     torch::Tensor pair_of, torch::Tensor tile_expert,
+                     torch::Tensor tile_row0, torch::Tensor ntiles,
+                     torch::Tensor hist, int64_t bm);
+void moe_tiled_gemm_fp8(torch::Tensor out, torch::Tensor a, torch::Tensor wq,
+                        torch::Tensor scale, torch::Tensor seg_start,
+                        torch::Tensor pair_of, torch::Tensor tile_expert,
+                        torch::Tensor tile_row0, torch::Tensor ntiles,
+                        c10::optional<torch::Tensor> topw, int64_t topk,
+                        bool gather, int64_t epilogue, int64_t bm, int64_t wn,
+                        int64_t wk, int64_t nt, int64_t u);
+void moe_tiled_gemm_mxfp4(torch::Tensor out, torch::Tensor a, torch::Tensor q,
+                          torch::Tensor scale, torch::Tensor seg_start,
+                          torch::Tensor pair_of, torch::Tensor tile_expert,
+                          torch::Tensor tile_row0, torch::Tensor ntiles,
+                          c10::optional<torch::Tensor> topw, int64_t topk,
+                          bool gather, int64_t epilogue, int64_t bm,
+                          int64_t wn, int64_t wk, int64_t nt, int64_t u);
+std::map<std::string, std::vector<std::tuple<int, int, int, int, int>>>
+moe_tile_configs();
 // ipc.hip
 torch::Tensor ipc_alloc(int64_t nbytes, int64_t device);
 py::bytes ipc_export(torch::Tensor t);
@@ -299,6 +320,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("u") = 1, py::arg("nt") = 2);
   // {"fp8" | "mxfp4": [(WPB, U, NT), ...]} they can launch
   m.def("moe_decode_quant_configs", &moe_decode_quant_configs);
+  // routed MoE for 64 < T <= 4096 with quantised experts: the route for many
+  // pairs, which also writes the map of bm-row tiles, and the expert-grouped
+  // tiled GEMM at point (BM, WN, WK, NT, U) of moe_tile_configs() with
+  // moe_routed_gemm's epilogues; moe_combine ends the chain. They raise on
+  // anything they do not handle - dispatch lives in ops.moe_tiled_mlp
+  m.def("moe_route_tiled", &moe_route_tiled, py::arg("topi"),
+        py::arg("seg_start"), py::arg("pair_of"), py::arg("tile_expert"),
+        py::arg("tile_row0"), py::arg("ntiles"), py::arg("hist"),
+        py::arg("bm"));
+  m.def("moe_tiled_gemm_fp8", &moe_tiled_gemm_fp8, py::arg("out"),
+        py::arg("a"), py::arg("wq"), py::arg("scale"), py::arg("seg_start"),
+        py::arg("pair_of"), py::arg("tile_expert"), py::arg("tile_row0"),
+        py::arg("ntiles"), py::arg("topw"), py::arg("topk"),
+        py::arg("gather"), py::arg("epilogue"), py::arg("bm") = 64,
+        py::arg("wn") = 4, py::arg("wk") = 1, py::arg("nt") = 2,
+        py::arg("u") = 1);
+  m.def("moe_tiled_gemm_mxfp4", &moe_tiled_gemm_mxfp4, py::arg("out"),
+        py::arg("a"), py::arg("q"), py::arg("scale"), py::arg("seg_start"),
+        py::arg("pair_of"), py::arg("tile_expert"), py::arg("tile_row0"),
+        py::arg("ntiles"), py::arg("topw"), py::arg("topk"),
+        py::arg("gather"), py::arg("epilogue"), py::arg("bm") = 64,
+        py::arg("wn") = 4, py::arg("wk") = 1, py::arg("nt") = 2,
+        py::arg("u") = 1);
+  // {"fp8" | "mxfp4": [(BM, WN, WK, NT, U), ...]} they can launch
+  m.def("moe_tile_configs", &moe_tile_configs);
   m.def("ipc_alloc", &ipc_alloc);
   m.def("ipc_export", &ipc_export);
   m.def("ipc_open", &ipc_open);

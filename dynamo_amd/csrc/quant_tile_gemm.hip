@@ -47,26 +47,24 @@
 // LDS (the x stages, free by then) and wave wk = 0 adds them in wave order.
 // No atomics: row m of y does not depend on M or BM and runs are
 // bit-reproducible.
-#include "skinny_gemm_impl.h"
+//
+// The main loop lives in quant_tile_gemm_impl.h, with the source of the x
+// rows as a policy; moe_tile_gemm.hip runs it over expert segments.
+#include "quant_tile_gemm_impl.h"
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 namespace qtile {
 
-using skinny::int4v;
-
-// Built without the packed fp32 VALU forms, as moe_decode.hip is.
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute push(                                               \
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
 
-template <class F, int BM, int WK>
-constexpr int kLdsBytes = 2 * WK * BM * F::KSTEP * 2;   // two x stages
-
-// Requires K % (WK * F::KSTEP * U) == 0, M >= 1, N % 16 == 0 (N % 32 if
-// GLU), gridDim.x = column blocks * mtiles, kLdsBytes of dynamic LDS. Tile
-// columns >= N read column N - 1 and are not stored.
+// The identity instantiation of quant_tile_gemm_impl.h's main loop: slab row
+// r is row m0 + r of x. Requires K % (WK * F::KSTEP * U) == 0, M >= 1,
+// N % 16 == 0 (N % 32 if GLU), gridDim.x = column blocks * mtiles, kLdsBytes
+// of dynamic LDS. Tile columns >= N read column N - 1 and are not stored.
 template <class F, int BM, int WN, int WK, int NT, int U, int NTL, int GLU>
 __global__ __launch_bounds__(WN * WK * 64) void quant_tile_gemm_kernel(
     const short* __restrict__ x,               // [M, K] bf16 row-major
@@ -74,27 +72,11 @@ __global__ __launch_bounds__(WN * WK * 64) void quant_tile_gemm_kernel(
     const typename F::scale_t* __restrict__ scale,
     short* __restrict__ y,                     // [M, N] ([M, N / 2] if GLU)
     int M, int N, int K, int mtiles) {
-  static_assert(!GLU || NT % 2 == 0, "GLU pairs gate and up tiles");
-  static_assert(BM % 16 == 0 && WN * WK <= 8, "at most 512 threads");
   constexpr int MT = BM / 16;
-  constexpr int T = WN * WK * 64;
-  constexpr int RB = F::KSTEP * 2;          // bytes per slab row
-  constexpr int SLAB = BM * RB;             // one k-slice of one stage
-  constexpr int STAGE = WK * SLAB;
-  constexpr int CPR = F::KSTEP / 8;         // 16 B chunks per slab row
-  constexpr int RPP = T / CPR;              // rows per copy pass
-  constexpr int CP = WK * BM / RPP;         // copy passes per step
-  static_assert(T % CPR == 0 && BM % RPP == 0, "a pass stays in one slice");
-  static_assert(kLdsBytes<F, BM, WK> <= 160 * 1024, "gfx950 LDS");
-  static_assert((WK - 1) * WN * NT * MT * 1024 <= kLdsBytes<F, BM, WK>,
-                "the parked accumulators fit the x stages");
   extern __shared__ __attribute__((aligned(16))) char lds[];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wn = wid % WN;                // column group
-  const int wk = wid / WN;                // k-slice
+  const int lane = threadIdx.x & 63;
+  const int wn = (threadIdx.x >> 6) % WN;  // column group
   const int lr = lane & 15;
   const int lg = lane >> 4;
   constexpr int NTO = GLU ? NT / 2 : NT;  // column tiles of y per wave
@@ -104,152 +86,11 @@ __global__ __launch_bounds__(WN * WK * 64) void quant_tile_gemm_kernel(
   // columns (it must keep the block's barriers) and stores nothing
   const int n0 = ((blockIdx.x / mtiles) * WN + wn) * NTO * 16;
 
-  const int kw = K / WK;                  // K per k-slice
-  const int steps = kw / F::KSTEP;
-
-  const typename F::welem* wp[NT][F::LOADS];
-#pragma unroll
-  for (int t = 0; t < NT; t++)
-#pragma unroll
-    for (int h = 0; h < F::LOADS; h++) {
-      int col = n0 + (t % NTO) * 16 + F::w_row(lane, h);
-      col = col < NO ? col : NO - 1;
-      if (GLU && t >= NTO) col += NO;   // the up row of that column
-      wp[t][h] = w + (size_t)col * (K / F::WPACK) +
-                 (wk * kw) / F::WPACK + F::w_k(lane);
-    }
-  const typename F::scale_t* sp[NT];
-  if constexpr (F::BLOCK_SCALED) {
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-      int col = n0 + (t % NTO) * 16 + lr;
-      col = col < NO ? col : NO - 1;
-      if (GLU && t >= NTO) col += NO;
-      sp[t] = scale + ((size_t)col * K + wk * kw) / 32;
-    }
-  }
-  const typename F::Sel sel = F::sel(lane);
-
   f32x4 acc[NT][MT];
-#pragma unroll
-  for (int t = 0; t < NT; t++)
-#pragma unroll
-    for (int m = 0; m < MT; m++) acc[t][m] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // ---- the x copy: chunk cc of rows cr + RPP * pass ----
-  const int cr = tid / CPR, cc = tid % CPR;
-  // only dereferenced for rows < M
-  const short* xc = x + (size_t)(m0 + cr) * K + cc * 8;
-  auto fetch_x = [&](int4v (&v)[CP], int d) {
-#pragma unroll
-    for (int c = 0; c < CP; c++) {
-      const int rr = (c * RPP) % BM, sl = (c * RPP) / BM;
-      v[c] = int4v{0, 0, 0, 0};
-      if (m0 + cr + rr < M)
-        v[c] = *reinterpret_cast<const int4v*>(xc + (size_t)rr * K + sl * kw +
-                                               d * F::KSTEP);
-    }
-  };
-  auto store_x = [&](const int4v (&v)[CP], int stage) {
-#pragma unroll
-    for (int c = 0; c < CP; c++) {
-      const int row = cr + (c * RPP) % BM, sl = (c * RPP) / BM;
-      *reinterpret_cast<int4v*>(lds + stage * STAGE + sl * SLAB + row * RB +
-                                ((cc ^ (row & 15)) << 4)) = v[c];
-    }
-  };
-
-  int4v rbuf[NT][U][F::LOADS];
-  typename F::Aux auxbuf[NT][U];
-  auto load_w = [&](int4v (&r)[F::LOADS], typename F::Aux& ax, int t, int d) {
-#pragma unroll
-    for (int h = 0; h < F::LOADS; h++)
-      r[h] = skinny::ldw<NTL>(wp[t][h] + d * (F::KSTEP / F::WPACK));
-    if constexpr (F::BLOCK_SCALED)
-      ax = *reinterpret_cast<const typename F::Aux*>(sp[t] +
-                                                     d * (F::KSTEP / 32));
-  };
-  // A fragment of (m, s): one ds_read_b128 at row 16 m + lr, whose
-  // r & 15 is lr. x_k / 8 and x_step(s) / 8 have no bit in common.
-  const char* abase = lds + wk * SLAB + lr * RB;
-  const int ach = F::x_k(lane) / 8;
-  auto consume = [&](int stage, const int4v (&r)[NT][F::LOADS],
-                     const typename F::Aux (&ax)[NT]) {
-#pragma unroll
-    for (int s = 0; s < F::FRAGS; s++) {
-      bf16x8 b[NT];
-#pragma unroll
-      for (int t = 0; t < NT; t++) b[t] = F::b_frag(s, r[t], sel, ax[t]);
-      const char* ap = abase + stage * STAGE +
-                       (((ach + F::x_step(s) / 8) ^ lr) << 4);
-#pragma unroll
-      for (int m = 0; m < MT; m++) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(ap + m * 16 * RB);
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-          acc[t][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[t],
-                                                              acc[t][m],
-                                                              0, 0, 0);
-      }
-    }
-  };
-
-  int4v xv[CP];
-  fetch_x(xv, 0);
-#pragma unroll
-  for (int u = 0; u < U; u++)
-#pragma unroll
-    for (int t = 0; t < NT; t++) load_w(rbuf[t][u], auxbuf[t][u], t, u);
-  store_x(xv, 0);
-  __syncthreads();
-  for (int d = 0; d < steps; d += U) {
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int step = d + u;
-      const int stage = step & 1;
-      const bool more = step + 1 < steps;
-      if (more) fetch_x(xv, step + 1);
-      int4v r[NT][F::LOADS];
-      typename F::Aux ax[NT];
-#pragma unroll
-      for (int t = 0; t < NT; t++) {
-#pragma unroll
-        for (int h = 0; h < F::LOADS; h++) r[t][h] = rbuf[t][u][h];
-        ax[t] = auxbuf[t][u];
-        if (step + U < steps) load_w(rbuf[t][u], auxbuf[t][u], t, step + U);
-      }
-      consume(stage, r, ax);
-      if (more) store_x(xv, stage ^ 1);
-      // step's reads of `stage` are done before step + 1 overwrites it
-      __syncthreads();
-    }
-  }
-
-  // Cross-slice reduction in wave order; the x stages are free: the loop's
-  // last barrier follows every read of them.
-  if constexpr (WK > 1) {
-    f32x4* red = reinterpret_cast<f32x4*>(lds);
-    if (wk > 0) {
-#pragma unroll
-      for (int t = 0; t < NT; t++)
-#pragma unroll
-        for (int m = 0; m < MT; m++)
-          red[((((wk - 1) * WN + wn) * NT + t) * MT + m) * 64 + lane] =
-              acc[t][m];
-    }
-    __syncthreads();
-    if (wk > 0) return;
-#pragma unroll
-    for (int r = 0; r < WK - 1; r++)
-#pragma unroll
-      for (int t = 0; t < NT; t++)
-#pragma unroll
-        for (int m = 0; m < MT; m++) {
-          const f32x4 o = red[(((r * WN + wn) * NT + t) * MT + m) * 64 + lane];
-          acc[t][m].x += o.x; acc[t][m].y += o.y;
-          acc[t][m].z += o.z; acc[t][m].w += o.w;
-        }
-  }
+  const DenseRows<F, BM, WN, WK> rows(x, m0, M, K);
+  if (!tile_gemm_mainloop<F, BM, WN, WK, NT, U, NTL, GLU>(
+          acc, rows, w, scale, NO, K, n0, lds))
+    return;
 
   // C layout: lane holds y[m0 + 16 m + lg*4 + i][tilecol + lr], i = 0..3.
   if constexpr (GLU) {

@@ -47,8 +47,25 @@ class ModelRunner:
                     f"{wd} weights cannot be combined with moe_ep: the "
                     "expert-parallel route slices bf16 expert tensors on the "
                     "host")
-            if (m.arch == "mixtral" and cfg.max_num_seqs > ops.MOE_DECODE_MAX_T
-                    and cfg.enable_hip_graphs):
+            # with the tiled route switched on (DYNAMO_MOE_TILED) a batch up
+            # to MOE_TILE_MAX_T stays on the device as well
+            tiled = m.arch == "mixtral" and ops.moe_tiled_enabled() and all(
+                ops.moe_tile_config(n, k, ops.MOE_DECODE_MAX_T + 1,
+                                    m.num_experts_per_tok, m.num_experts, wd)
+                for n, k in ((2 * m.intermediate_size // self.tp.size,
+                              m.hidden_size),
+                             (m.hidden_size,
+                              m.intermediate_size // self.tp.size)))
+            if (tiled and cfg.enable_hip_graphs
+                    and cfg.max_num_seqs > ops.MOE_TILE_MAX_T):
+                raise ValueError(
+                    f"{wd} Mixtral experts run the routed kernels up to "
+                    f"{ops.MOE_TILE_MAX_T} tokens with DYNAMO_MOE_TILED on; a "
+                    "larger batch takes the host-side expert loop, which "
+                    f"cannot be captured: max_num_seqs = {cfg.max_num_seqs} "
+                    "needs hipGraphs off")
+            if (m.arch == "mixtral" and cfg.enable_hip_graphs
+                    and cfg.max_num_seqs > ops.MOE_DECODE_MAX_T and not tiled):
                 raise ValueError(
                     f"{wd} Mixtral experts decode through the routed kernels "
                     f"up to {ops.MOE_DECODE_MAX_T} tokens; a larger batch "

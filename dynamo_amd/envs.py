@@ -68,6 +68,13 @@ ENV_VARS = {
         "expert-grouped gate/up GEMM with SwiGLU, weighted down GEMM, "
         "combine; idle experts' weights are not read). Default: the padded "
         "bmm route",
+    "DYNAMO_MOE_TILED":
+        "1 = fp8 / mxfp4 Mixtral experts above the routed decode kernels' 64 "
+        "tokens, up to ops.MOE_TILE_MAX_T, run the routed tiled kernels "
+        "(csrc/moe_tile_gemm.hip: device-side route with a tile map, "
+        "expert-grouped tiled gate/up GEMM with SwiGLU, weighted down GEMM, "
+        "combine; no host read, hipGraph-safe) instead of the host-side "
+        "expert loop. Default: off",
     "DYNAMO_MOE_MFMA": "0 = VALU grouped MoE GEMM",
     "DYNAMO_MOE_GRAPHS": "0 = exclude MoE layers from hipGraph capture",
     "DYNAMO_ROCTX": "1 = roctx range annotations for rocprofv3 traces",

@@ -89,6 +89,15 @@ class MoEMLP(torch.nn.Module):
             out = ops.moe_decode_mlp(x, topw, topi, self.w_gate_up,
                                      self.w_down)
             return self.tp.all_reduce(out)
+        if (quant and not self.ep and ops.moe_tiled_enabled()
+                and ops.moe_tiled_ready(x, self.topk, self.w_gate_up,
+                                        self.w_down)):
+            # routed, tiled (csrc/moe_tile_gemm.hip): the same chain above
+            # the decode kernels' T, on expert-grouped tiled GEMMs. Opt-in;
+            # device-side and static, so hipGraph-safe.
+            out = ops.moe_tiled_mlp(x, topw, topi, self.w_gate_up,
+                                    self.w_down)
+            return self.tp.all_reduce(out)
         topw = topw.to(x.dtype)
         if quant:
             return self.tp.all_reduce(self._expert_loop(x, topw, topi))

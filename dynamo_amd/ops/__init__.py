@@ -1022,6 +1022,199 @@ def moe_decode_mlp(x, topw, topi, w_gate_up, w_down):
     return moe_down_combine(act, w_down, seg_start, pair_of, topw.float())
 
 
+# --------------------------------------------------------------------------
+# Routed MoE, tiled (csrc/moe_tile_gemm.hip): quantised experts above the
+# decode route's 64 tokens. A route for up to MOE_TILE_KERNEL_MAX_T * 8 pairs
+# that also writes the map of BM-row tiles, the expert-grouped tiled GEMM
+# (the dense tiled kernel's main loop over expert segments) for gate/up +
+# SwiGLU and for the gate-weighted down projection, and moe_combine: five
+# launches, no host read, hipGraph-safe. Opt-in (DYNAMO_MOE_TILED=1 /
+# set_moe_tiled): off, such calls take MoEMLP._expert_loop as before.
+MOE_TILE_KERNEL_MAX_T = 4096
+# The dispatch limit: the largest swept T (128 .. 2048) at which the route was
+# ahead of the host loop on the full and the TP-2 shapes in both runs of
+# `kernel_bench.py --which moe_tiled_sweep` (profiles/README.md, "Routed MoE,
+# tiled"): all of them, 1.2-4.7x; nothing above 2048 was measured.
+MOE_TILE_MAX_T = 2048
+MOE_TILE_BMS: tuple = (32, 64, 128)
+# pairs per block of the route kernels (ROUTE_THREADS of the kernel file): the
+# histogram scratch holds one row of E counts per block
+MOE_TILE_ROUTE_BLOCK = 512
+# (BM, WN, WK, NT, U) points of moe_tiled_gemm_fp8 / _mxfp4; they need
+# K % (WK * kstep * U) == 0. Copies of the kernel file's tables, checked
+# against hip().moe_tile_configs(). The first point of every BM accepts every
+# K % kstep == 0.
+MOE_TILE_CONFIGS: dict = {
+    "fp8": ((32, 4, 1, 2, 1), (64, 4, 1, 2, 1), (128, 4, 1, 2, 1),
+            (32, 4, 2, 2, 2), (64, 4, 2, 2, 2), (128, 4, 2, 2, 2),
+            (32, 8, 1, 2, 2), (64, 8, 1, 2, 2), (128, 8, 1, 2, 2)),
+    "mxfp4": ((32, 4, 1, 2, 1), (64, 4, 1, 2, 1), (128, 4, 1, 2, 1),
+              (32, 4, 2, 2, 1), (64, 4, 2, 2, 1),
+              (32, 8, 1, 2, 1), (64, 8, 1, 2, 1), (128, 8, 1, 2, 1)),
+}
+# format -> (N, K) of an expert's weight -> the (WN, WK, NT, U) at BM = 32,
+# 64, 128, for the Mixtral-8x7B expert shapes of MOE_DECODE_SHAPES that
+# `kernel_bench.py --which moe_tiled_sweep` covers (profiles/README.md,
+# "Routed MoE, tiled"); a shape not listed takes moe_tile_config's fallback.
+MOE_TILE_SHAPES: dict = {
+    "fp8": {
+        (28672, 4096): ((8, 1, 2, 2), (8, 1, 2, 2), (8, 1, 2, 2)),  # gate/up
+        (14336, 4096): ((4, 1, 2, 1), (4, 1, 2, 1), (8, 1, 2, 2)),  # ..., TP 2
+        (4096, 14336): ((4, 2, 2, 2), (4, 1, 2, 1), (8, 1, 2, 2)),  # down
+        (4096, 7168): ((4, 2, 2, 2), (4, 1, 2, 1), (8, 1, 2, 2)),   # ..., TP 2
+    },
+    "mxfp4": {
+        (28672, 4096): ((8, 1, 2, 1), (8, 1, 2, 1), (8, 1, 2, 1)),
+        (14336, 4096): ((4, 1, 2, 1), (8, 1, 2, 1), (8, 1, 2, 1)),
+        (4096, 14336): ((4, 1, 2, 1), (8, 1, 2, 1), (8, 1, 2, 1)),
+        (4096, 7168): ((4, 1, 2, 1), (8, 1, 2, 1), (8, 1, 2, 1)),
+    },
+}
+
+_moe_tiled_override: "bool | None" = None
+
+
+def set_moe_tiled(on: "bool | None") -> None:
+    """In-process override of DYNAMO_MOE_TILED (None = follow the env)."""
+    global _moe_tiled_override
+    _moe_tiled_override = on
+
+
+def moe_tiled_enabled() -> bool:
+    if _moe_tiled_override is not None:
+        return _moe_tiled_override
+    from dynamo_amd import envs
+    return envs.get("DYNAMO_MOE_TILED", False, bool)
+
+
+def moe_tile_bm(T: int, topk: int, E: int) -> int:
+    """The tile height for T tokens: the smallest BM that holds the mean
+    segment T topk / E in one tile, 128 above that."""
+    mean = T * topk / E
+    return next((bm for bm in MOE_TILE_BMS if mean <= bm), MOE_TILE_BMS[-1])
+
+
+def moe_tile_config(N: int, K: int, T: int, topk: int, E: int, fmt: str):
+    """The (BM, WN, WK, NT, U) the tiled routed GEMM of `fmt` runs an expert
+    weight [N, K] at: BM from the mean segment size, the rest from the
+    shape's entry in MOE_TILE_SHAPES, else (or where K does not allow the
+    entry) the deepest point of that BM (largest K step WK * kstep * U, the
+    earlier one among equals) that divides K. None if the kernel does not
+    take the call."""
+    if fmt not in MOE_TILE_CONFIGS:
+        return None
+    kstep = MOE_DECODE_FORMATS[fmt][0]
+    if not (MOE_DECODE_MAX_T < T <= MOE_TILE_KERNEL_MAX_T
+            and 1 <= topk <= MOE_DECODE_MAX_TOPK and 1 <= E <= MOE_DECODE_MAX_E
+            and N >= 16 and N % 16 == 0 and K >= kstep and K % kstep == 0):
+        return None
+    bm = moe_tile_bm(T, topk, E)
+    fits = [c for c in MOE_TILE_CONFIGS[fmt]
+            if c[0] == bm and K % (c[2] * kstep * c[4]) == 0]
+    entry = MOE_TILE_SHAPES[fmt].get((N, K))
+    if entry is not None:
+        point = (bm, *entry[MOE_TILE_BMS.index(bm)])
+        if point in fits:
+            return point
+    return max(fits, key=lambda c: c[2] * c[4])
+
+
+def moe_route_tiled(topi: torch.Tensor, E: int, BM: int):
+    """moe_route for up to MOE_TILE_KERNEL_MAX_T tokens, with the map of
+    BM-row tiles: -> (seg_start [E + 1], pair_of [T K], tile_expert,
+    tile_row0, ntiles), int32. On the GPU the tile arrays hold
+    T K // BM + min(E, T K) entries of which the first ntiles [1] (a device
+    tensor) are written; on the CPU they hold exactly ntiles (an int)."""
+    if not topi.is_cuda:
+        seg_start, pair_of = torch_ref.moe_route(topi, E)
+        return (seg_start, pair_of, *torch_ref.moe_tile_map(seg_start, BM))
+    P = topi.numel()
+
+    def i32(n):
+        return torch.empty(n, dtype=torch.int32, device=topi.device)
+    max_tiles = P // BM + min(E, P)
+    route = (i32(E + 1), i32(P), i32(max_tiles), i32(max_tiles), i32(1))
+    hist = i32(-(-P // MOE_TILE_ROUTE_BLOCK) * E)
+    hip().moe_route_tiled(topi.contiguous(), *route, hist, BM)
+    return route
+
+
+def _moe_tiled_cfg(w, T, topk, cfg):
+    fmt = moe_format(w)
+    cfg = cfg or moe_tile_config(w.shape[1], w.shape[2], T, topk, w.shape[0],
+                                 fmt)
+    if cfg is None:
+        raise ValueError(f"no tiled routed MoE GEMM for {fmt} expert weights "
+                         f"{tuple(w.shape)} at T = {T}")
+    return cfg
+
+
+def moe_tiled_gemm(a, w, route, topk: int, *, gather: bool, glu: bool,
+                   cfg=None):
+    """moe_routed_gemm on the tiled kernel: `route` is moe_route_tiled's
+    result at cfg's BM, w an Fp8ExpertWeight / Mxfp4ExpertWeight."""
+    seg_start, pair_of = route[:2]
+    if not a.is_cuda:
+        return torch_ref.moe_routed_gemm(a, _moe_effective(w, a.dtype),
+                                         seg_start, pair_of, topk, gather,
+                                         glu)
+    P = pair_of.numel()
+    cfg = _moe_tiled_cfg(w, P // topk, topk, cfg)
+    y = torch.empty(P, w.shape[1] // 2 if glu else w.shape[1], dtype=a.dtype,
+                    device=a.device)
+    getattr(hip(), "moe_tiled_gemm_" + moe_format(w))(
+        y, a, w.q, w.scale, *route, None, topk, gather, 1 if glu else 0, *cfg)
+    return y
+
+
+def moe_tiled_down_combine(act, w_down, route, topw, cfg=None):
+    """moe_down_combine on the tiled kernel: fp32 rows times the gate weight,
+    summed per token in ascending j and rounded once."""
+    seg_start, pair_of = route[:2]
+    if not act.is_cuda:
+        return torch_ref.moe_down_combine(
+            act, _moe_effective(w_down, act.dtype), seg_start, pair_of, topw)
+    T, topk = topw.shape
+    cfg = _moe_tiled_cfg(w_down, T, topk, cfg)
+    part = torch.empty(T * topk, w_down.shape[1], dtype=torch.float32,
+                       device=act.device)
+    getattr(hip(), "moe_tiled_gemm_" + moe_format(w_down))(
+        part, act, w_down.q, w_down.scale, *route, topw.contiguous(), topk,
+        False, 2, *cfg)
+    out = torch.empty(T, w_down.shape[1], dtype=act.dtype, device=act.device)
+    hip().moe_combine(out, part, topk)
+    return out
+
+
+def moe_tiled_ready(x, topk: int, w_gate_up, w_down) -> bool:
+    """Whether moe_tiled_mlp takes the call on the GPU: 64 < T <=
+    MOE_TILE_MAX_T, quantised weights of one format stored as the kernels
+    ask, bf16 contiguous x, and a configuration for both GEMMs."""
+    T = x.shape[0]
+    E, N, K = w_gate_up.shape
+    fmt = moe_format(w_gate_up)
+    return (x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16
+            and fmt != "bf16" and moe_format(w_down) == fmt
+            and _moe_weight_ready(w_gate_up, fmt)
+            and _moe_weight_ready(w_down, fmt)
+            and MOE_DECODE_MAX_T < T <= MOE_TILE_MAX_T
+            and N % 32 == 0 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0
+            and moe_tile_config(N, K, T, topk, E, fmt) is not None
+            and moe_tile_config(w_down.shape[1], w_down.shape[2], T, topk, E,
+                                fmt) is not None)
+
+
+def moe_tiled_mlp(x, topw, topi, w_gate_up, w_down):
+    """moe_decode_mlp for 64 < T <= MOE_TILE_MAX_T and quantised experts, on
+    the tiled kernels; the CPU computes through torch_ref with effective()."""
+    T, topk = topi.shape
+    E = w_gate_up.shape[0]
+    route = moe_route_tiled(topi, E, moe_tile_bm(T, topk, E))
+    act = moe_tiled_gemm(x, w_gate_up, route, topk, gather=True, glu=True)
+    return moe_tiled_down_combine(act, w_down, route, topw.float())
+
+
 def gather_pages(staging, cache, page_ids):
     if cache.is_cuda:
         hip().gather_pages(staging, cache, page_ids)

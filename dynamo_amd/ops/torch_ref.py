@@ -323,6 +323,18 @@ def moe_route(topi, E):
     return seg_start, pair_of
 
 
+def moe_tile_map(seg_start, BM):
+    """seg_start [E + 1] -> (tile_expert [n], tile_row0 [n], n): the BM-row
+    tiles of the non-empty segments, ascending in expert and row. At most
+    P // BM + min(E, P) of them exist for P = seg_start[E] sorted rows."""
+    seg = seg_start.tolist()
+    tiles = [(e, r) for e in range(len(seg) - 1)
+             for r in range(seg[e], seg[e + 1], BM)]
+    te, tr = (torch.tensor([t[i] for t in tiles], dtype=torch.int32,
+                           device=seg_start.device) for i in (0, 1))
+    return te, tr, len(tiles)
+
+
 def _moe_segments(a, w, seg_start, pair_of, topk, gather):
     """fp32 [P, N]: sorted row i times its expert's weight."""
     rows = a[pair_of.long() // topk] if gather else a

@@ -32,6 +32,7 @@ hip_sources = [
         "logits_process.hip",
         "moe.hip",
         "moe_decode.hip",
+        "moe_tile_gemm.hip",
         "lora.hip",
         "ipc.hip",
         "probe.hip",
