@@ -160,6 +160,104 @@ def bench_mq_attn(S=16, Hkv=8, G=8, ps=64, ctxs=(8192, 2048),
             del caches
 
 
+def bench_shared_prefix(Hkv=8, G=8, ps=64, ctx=8192,
+                        shapes=((16, 1), (64, 4)),
+                        shared_lens=(2048, 4096, 6144), rounds=3, window=0.2):
+    """Decode rows that share leading pages: ops.paged_attention_decode_shared
+    (plan built once on the host, as the graph runner does; phase 1 and the
+    chunk merge timed) against ops.paged_attention_decode on the same
+    tensors, i.e. the same page table with the groups' common page ids.
+    `shapes` is (batch, groups): each group's rows share `shared` tokens and
+    own the rest of their ctx. Cache-cold: call i reads copy i % R of the K/V
+    caches, R copies together past 640 MB of distinct pages (the Infinity
+    Cache holds 256 MB). Device events around >= `window` s of back-to-back
+    eager calls, the two alternated `rounds` times, best of the rounds.
+    `streamed` is what each kernel's blocks load of K and V: batch * ctx
+    tokens for the decode kernel, the plan's item ranges for the shared one."""
+    hd, Hq, dev = 128, Hkv * G, "cuda"
+    scale = hd ** -0.5
+
+    def event_time(fn, n):
+        start, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        start.record()
+        for i in range(n):
+            fn(i)
+        end.record()
+        end.synchronize()
+        return start.elapsed_time(end) * 1e-3 / n
+
+    for fp8 in (False, True):
+        store = torch.float8_e4m3fn if fp8 else torch.bfloat16
+        tok_bytes = 2 * Hkv * hd * (1 if fp8 else 2)        # K + V
+        for B, groups in shapes:
+            scratch = ops.DecodeScratch(B, Hq, hd, ctx, dev)
+            chunk = scratch.chunk_tokens
+            q = torch.randn(B, Hq, hd, dtype=torch.bfloat16, device=dev)
+            ctxl = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+            for shared in shared_lens:
+                per, sp, tp = B // groups, shared // ps, (ctx - shared) // ps
+                pages, nxt = [], 0
+                for g in range(groups):
+                    common = list(range(nxt, nxt + sp))
+                    nxt += sp
+                    for _ in range(per):
+                        pages.append(common + list(range(nxt, nxt + tp)))
+                        nxt += tp
+                plan = ops.shared_prefix_plan(pages, [ctx] * B, chunk, ps, G,
+                                              B + B // 2)
+                item_tokens = sum(
+                    (ctx if t1 < 0 else t1) - t0
+                    for (t0, t1), r0 in zip(plan[1].tolist(),
+                                            plan[0][:, 0].tolist()) if r0 >= 0)
+                plan = (plan[0].to(dev), plan[1].to(dev), plan[2])
+                pt = torch.tensor(pages, dtype=torch.int32, device=dev)
+                R = max(1, -(-640_000_000 // (nxt * ps * tok_bytes)))
+                caches = []
+                for _ in range(R):
+                    k = torch.randn(nxt, Hkv, ps, hd, dtype=torch.bfloat16,
+                                    device=dev)
+                    v = torch.randn(nxt, Hkv, hd, ps, dtype=torch.bfloat16,
+                                    device=dev)
+                    caches.append((k.to(store), v.to(store)))
+
+                def decode(i):
+                    kc, vc = caches[i % R]
+                    return ops.paged_attention_decode(
+                        q, kc, vc, pt, ctxl, scale, scratch,
+                        v_transposed=True)
+
+                def shared_fn(i):
+                    kc, vc = caches[i % R]
+                    return ops.paged_attention_decode_shared(
+                        q, kc, vc, pt, ctxl, plan, scale, scratch)
+
+                diff = float((shared_fn(0).float()
+                              - decode(0).float()).abs().max())
+                fns = {"decode": decode, "shared": shared_fn}
+                n = {}
+                for name, fn in fns.items():
+                    event_time(fn, 2 * R)                       # warm-up
+                    n[name] = max(2 * R, int(window / event_time(fn, 2 * R)))
+                ts = {name: [] for name in fns}
+                for _ in range(rounds):
+                    for name, fn in fns.items():
+                        ts[name].append(event_time(fn, n[name]))
+                t = {name: min(v) for name, v in ts.items()}
+                gb_d = B * ctx * tok_bytes / 1e9
+                gb_s = item_tokens * tok_bytes / 1e9
+                print(f"shared_prefix {'fp8 ' if fp8 else 'bf16'} B{B} "
+                      f"groups {groups} Hq{Hq}/{Hkv} ctx{ctx} shared {shared} "
+                      f"R={R} members {plan[2]}: decode "
+                      f"{t['decode']*1e6:7.1f}-{max(ts['decode'])*1e6:7.1f} us"
+                      f" streamed {gb_d*1e3:5.0f} MB {gb_d/t['decode']:5.0f} "
+                      f"GB/s | shared {t['shared']*1e6:7.1f}-"
+                      f"{max(ts['shared'])*1e6:7.1f} us streamed "
+                      f"{gb_s*1e3:5.0f} MB {gb_s/t['shared']:5.0f} GB/s | "
+                      f"decode/shared {t['decode']/t['shared']:5.2f}x | "
+                      f"max |shared - decode| {diff:.1e}", flush=True)
+                del caches
+
+
 def bench_prefill_attn(S=8192, Hq=32, Hkv=8, ps=64, v_transposed=False):
     hd = 128
     npages = (S + ps - 1) // ps
@@ -873,6 +971,8 @@ if __name__ == "__main__":
         bench_prefill_attn(S=2048, Hq=64)
     if w in ("all", "mq_attn"):
         bench_mq_attn()
+    if w in ("all", "shared_prefix"):
+        bench_shared_prefix()
     if w in ("all", "append"):
         bench_kv_append()
     if w in ("all", "sample"):

@@ -45,6 +45,13 @@ void paged_attention_multiquery(
     torch::Tensor seq_q_len, torch::Tensor seq_ctx_len, torch::Tensor row_ctx,
     torch::Tensor partial, torch::Tensor ml, double scale,
     int64_t chunk_tokens, int64_t max_q_len);
+// attention_shared_prefix.hip
+void paged_attention_decode_shared(
+    torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
+    torch::Tensor vcache, torch::Tensor page_table, torch::Tensor ctx_lens,
+    torch::Tensor item_rows, torch::Tensor item_range, torch::Tensor partial,
+    torch::Tensor ml, double scale, int64_t chunk_tokens,
+    int64_t max_members);
 // attention_prefill.hip
 void attention_prefill_paged(torch::Tensor out, torch::Tensor q,
                              torch::Tensor kcache, torch::Tensor vcache,
@@ -202,6 +209,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seq_ctx_len"), py::arg("row_ctx"), py::arg("partial"),
         py::arg("ml"), py::arg("scale"), py::arg("chunk_tokens"),
         py::arg("max_q_len"));
+  // decode rows that share leading pages stream them once (d-major V pages,
+  // hd 128, max_members * G <= 64): item_rows [W, 64 / G] names the batch
+  // rows of each work item (-1 pads; row 0 == -1 = unused item), item_range
+  // [W, 2] its tokens (t_end -1 = the first row's ctx_len); the items must
+  // cover every (row, chunk) below ctx exactly once - ops.shared_prefix_plan
+  m.def("paged_attention_decode_shared", &paged_attention_decode_shared,
+        py::arg("out"), py::arg("q"), py::arg("kcache"), py::arg("vcache"),
+        py::arg("page_table"), py::arg("ctx_lens"), py::arg("item_rows"),
+        py::arg("item_range"), py::arg("partial"), py::arg("ml"),
+        py::arg("scale"), py::arg("chunk_tokens"), py::arg("max_members"));
   m.def("attention_prefill_paged", &attention_prefill_paged,
         py::arg("out"), py::arg("q"), py::arg("kcache"), py::arg("vcache"),
         py::arg("page_table"), py::arg("tile_seq"), py::arg("tile_q0"),

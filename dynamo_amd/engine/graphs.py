@@ -48,8 +48,17 @@ class GraphRunner:
         # adapter mix changes refills it and replays the same graph.
         self.lora_slots = torch.full((B,), -1, dtype=torch.int32, device=dev)
         self.has_lora = False
-        # (bucket, has_lora) -> graph: a batch with no adapter replays a
-        # graph without the LoRA kernels and pays nothing
+        # shared-prefix attention (opt-in): the work items of the current
+        # batch, in persistent buffers of bc + bc // 2 items per bucket
+        # (every row's own item plus at most one prefix item per two rows).
+        # has_shared is the kernel's column-tile count for the batch, 0 when
+        # no rows share a prefix.
+        self.shared_items: Dict[int, tuple] = {}
+        self.has_shared = 0
+        # (bucket, has_lora) -> graph, or (bucket, has_lora, has_shared) for
+        # a batch with a shared prefix: a batch with no adapter replays a
+        # graph without the LoRA kernels, a batch without a shared prefix
+        # the graph with the per-row decode kernel; neither pays
         self.graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self._graph_pool = None
         # current batch composition
@@ -58,8 +67,16 @@ class GraphRunner:
         self._first_after_rebuild = True
 
     # ------------------------------------------------------------------
-    def _meta(self, bc: int, has_lora: bool = False) -> AttnMetadata:
+    def _meta(self, bc: int, has_lora: bool = False,
+              has_shared: int = 0) -> AttnMetadata:
+        shared = None
+        if has_shared:
+            # the launch takes has_shared column tiles: any plan whose items
+            # have at most this many members replays the same graph
+            G = self.runner.hq_local // self.runner.hkv_local
+            shared = (*self.shared_items[bc], has_shared * 16 // G)
         return AttnMetadata(
+            decode_shared=shared,
             lora_slots=self.lora_slots[:bc] if has_lora else None,
             lora_decode_rows=bc if has_lora else 0,
             slot_mapping=self.slot_mapping[:bc],
@@ -73,10 +90,10 @@ class GraphRunner:
         )
 
     @torch.inference_mode()
-    def _capture(self, bc: int, has_lora: bool = False):
+    def _capture(self, bc: int, has_lora: bool = False, has_shared: int = 0):
         model = self.runner.model
         kv_pool = self.runner.kv_pool
-        meta = self._meta(bc, has_lora)
+        meta = self._meta(bc, has_lora, has_shared)
         torch.cuda.synchronize()
         # warm up the exact op sequence on a side stream first
         s = torch.cuda.Stream()
@@ -91,7 +108,11 @@ class GraphRunner:
             self.logits[:bc] = model.compute_logits(h)
         if self._graph_pool is None:
             self._graph_pool = g.pool()
-        self.graphs[(bc, has_lora)] = g
+        self.graphs[self._key(bc, has_lora, has_shared)] = g
+
+    @staticmethod
+    def _key(bc: int, has_lora: bool, has_shared: int) -> tuple:
+        return (bc, has_lora, has_shared) if has_shared else (bc, has_lora)
 
     def _bucket(self, n: int) -> int:
         for b in BUCKETS:
@@ -127,12 +148,39 @@ class GraphRunner:
                 self.lora_slots[:n].copy_(
                     torch.tensor(slots_l, dtype=torch.int32))
         self.has_lora = has_lora
+        self.has_shared = self._plan_shared(reqs, pos)
         # pad rows: ctx 0 disables attention; slot -1 skips kv append
         if n < self.max_batch:
             self.ctx_lens[n:].fill_(0)
             self.slot_mapping[n:].fill_(-1)
         self.dirty = False
         self._first_after_rebuild = True
+
+    def _plan_shared(self, reqs: List[Request], pos: List[int]) -> int:
+        """Refill the bucket's work-item buffers for this batch; returns the
+        column tiles its plan needs, 0 without a shared prefix. The plan
+        holds until the next rebuild: ctx_lens only grows, and
+        patch_new_page touches only the rows' own tails."""
+        from dynamo_amd import ops
+        ready = getattr(self.runner, "shared_prefix_ready", None)
+        if not reqs or ready is None or not ready():
+            return 0
+        bc = self._bucket(len(reqs))
+        G = self.runner.hq_local // self.runner.hkv_local
+        plan = ops.shared_prefix_plan(
+            [r.kv.pages for r in reqs], [p + 1 for p in pos],
+            self.runner.decode_scratch.chunk_tokens, self.ps, G,
+            bc + bc // 2)
+        if plan is None:
+            return 0
+        if bc not in self.shared_items:
+            self.shared_items[bc] = (
+                torch.empty_like(plan[0], device=self.device),
+                torch.empty_like(plan[1], device=self.device))
+        self.shared_items[bc][0].copy_(plan[0])
+        self.shared_items[bc][1].copy_(plan[1])
+        tiles = -(-plan[2] * G // 16)
+        return 4 if tiles == 3 else tiles
 
     def patch_new_page(self, i: int, page_idx: int, page_id: int):
         """A sequence allocated a new page (host-side) — patch one cell."""
@@ -163,13 +211,13 @@ class GraphRunner:
         if not self.use_graphs:
             # persistent-buffer eager path (TP ranks: RCCL-in-graph capture
             # is not exercised; MoE: host-side tile lists aren't capturable)
-            meta = self._meta(bc, self.has_lora)
+            meta = self._meta(bc, self.has_lora, self.has_shared)
             h = self.runner.model.forward(self.input_ids[:bc],
                                           self.runner.kv_pool, meta)
             self.logits[:bc] = self.runner.model.compute_logits(h)
             return self.logits[:n]
-        key = (bc, self.has_lora)
+        key = self._key(bc, self.has_lora, self.has_shared)
         if key not in self.graphs:
-            self._capture(bc, self.has_lora)
+            self._capture(bc, self.has_lora, self.has_shared)
         self.graphs[key].replay()
         return self.logits[:n]

@@ -148,6 +148,15 @@ class ModelRunner:
                 min(cfg.max_num_seqs * ops.MQ_MAX_Q, cfg.max_batched_tokens),
                 self.hq_local, m.head_dim, cfg.max_model_len, self.device)
 
+    def shared_prefix_ready(self) -> bool:
+        """Decode steps may take the shared-prefix attention kernel: the
+        switch is on and the engine's layout is the kernel's."""
+        return (self.device.type == "cuda" and ops.shared_prefix_attn_enabled()
+                and ops.shared_prefix_ready(
+                    self.hq_local, self.hkv_local, self.cfg.model.head_dim,
+                    self.cfg.page_size, self.v_transposed,
+                    self.cfg.kv_torch_dtype))
+
     def _auto_pages(self) -> int:
         m = self.cfg.model
         page_bytes = (m.num_layers * 2 * self.hkv_local * self.cfg.page_size
@@ -267,6 +276,14 @@ class ModelRunner:
             meta.embeds_rows = torch.tensor(embeds_rows, dtype=torch.int64,
                                             device=dev)
             meta.inputs_embeds = torch.cat(embeds_parts, 0).to(dev)
+        if nd and self.shared_prefix_ready():
+            plan = ops.shared_prefix_plan(
+                dec_tables, dec_ctx, self.decode_scratch.chunk_tokens, ps,
+                self.hq_local // self.hkv_local, nd + nd // 2)
+            if plan is not None:
+                meta.decode_shared = (plan[0].to(dev, non_blocking=True),
+                                      plan[1].to(dev, non_blocking=True),
+                                      plan[2])
         mq = self.multiquery_scratch
         if (qpos and mq is not None and ops.multiquery_attn_enabled()
                 and qpos <= mq.max_rows

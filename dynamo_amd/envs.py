@@ -51,6 +51,14 @@ ENV_VARS = {
         "head_dim 128) attends through the split-KV multi-query kernel "
         "(csrc/attention_multiquery.hip) instead of the prefill kernel. "
         "Default: off",
+    "DYNAMO_SHARED_PREFIX_ATTN":
+        "1 = decode rows whose page tables begin with the same pages (a "
+        "prefix-cache hit on a common prompt, at least one decode chunk "
+        "long) attend through the shared-prefix kernel "
+        "(csrc/attention_shared_prefix.hip), which streams the common pages "
+        "once per group of up to 64 / G rows; a step without such a group "
+        "runs the decode kernel as before (d-major V pages, head_dim 128). "
+        "Default: off",
     "DYNAMO_MAX_LORAS":
         "default of the worker's --max-loras: adapter-bank slots for "
         "per-request LoRA (default 0 = engine-level activation only)",

@@ -30,6 +30,10 @@ class AttnMetadata:
     decode_page_table: Optional[torch.Tensor] = None   # [Bd, maxp] int32
     decode_ctx_lens: Optional[torch.Tensor] = None     # [Bd] int32
     decode_scratch: Optional["ops.DecodeScratch"] = None
+    # (item_rows, item_range, max_members) on the device when decode rows
+    # share leading pages and take the shared-prefix kernel (opt-in, see
+    # ops.shared_prefix_plan); None = the per-row decode kernel
+    decode_shared: Optional[tuple] = None
     # prefill part
     num_prefill_tokens: int = 0
     prefill_page_table: Optional[torch.Tensor] = None  # [Bp, maxp] int32
@@ -243,7 +247,12 @@ class Attention(torch.nn.Module):
         qh = q.view(T, self.hq, self.hd)
         out = torch.empty_like(qh)
         nd = meta.num_decode
-        if nd:
+        if nd and meta.decode_shared is not None:
+            ops.paged_attention_decode_shared(
+                qh[:nd], kcache, vcache, meta.decode_page_table,
+                meta.decode_ctx_lens, meta.decode_shared, self.scale,
+                meta.decode_scratch, out=out[:nd])
+        elif nd:
             ops.paged_attention_decode(
                 qh[:nd], kcache, vcache, meta.decode_page_table,
                 meta.decode_ctx_lens, self.scale, meta.decode_scratch,

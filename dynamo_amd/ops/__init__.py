@@ -702,6 +702,123 @@ def paged_attention_multiquery(q, kcache, vcache, page_table, seq_q_start,
                                              v_transposed=v_transposed)
 
 
+# --------------------------------------------------------------------------
+# Shared-prefix decode attention (csrc/attention_shared_prefix.hip): decode
+# rows whose page tables begin with the same physical pages (the prefix cache
+# hands a common prompt's pages to every request that hits it) stream those
+# pages once, the rows folded onto the MFMA columns beside the GQA group.
+# Opt-in (DYNAMO_SHARED_PREFIX_ATTN=1 / set_shared_prefix_attn): off, and in
+# any step without such a group, decode runs the per-row kernel as before.
+SP_MAX_COLS = 64    # members * G: four 16-column MFMA tiles
+
+_shared_prefix_override: "bool | None" = None
+
+
+def set_shared_prefix_attn(on: "bool | None") -> None:
+    """In-process override of DYNAMO_SHARED_PREFIX_ATTN (None = follow the
+    env)."""
+    global _shared_prefix_override
+    _shared_prefix_override = on
+
+
+def shared_prefix_attn_enabled() -> bool:
+    if _shared_prefix_override is not None:
+        return _shared_prefix_override
+    from dynamo_amd import envs
+    return envs.get("DYNAMO_SHARED_PREFIX_ATTN", False, bool)
+
+
+def shared_prefix_ready(Hq: int, Hkv: int, head_dim: int, page_size: int,
+                        v_transposed: bool, kv_dtype) -> bool:
+    """Can the shared-prefix kernel serve this engine's decode steps?"""
+    if Hkv <= 0 or Hq % Hkv:
+        return False
+    return (v_transposed and 2 <= Hq // Hkv <= 16 and head_dim == 128
+            and page_size % 32 == 0 and page_size & (page_size - 1) == 0
+            and kv_dtype in (torch.bfloat16, torch.float8_e4m3fn))
+
+
+def shared_prefix_plan(page_lists, ctx_lens, chunk_tokens: int,
+                       page_size: int, G: int, capacity: int):
+    """Work items of the shared-prefix kernel for one decode batch, from host
+    values only (page id lists and context lengths per row): (item_rows
+    [capacity, R] int32, item_range [capacity, 2] int32, max_members) as host
+    tensors, R = SP_MAX_COLS // G, or None when no two rows share a chunk.
+
+    Rows are bucketed by their first chunk's page ids. A bucket's prefix_len
+    is the common leading page run of all its rows in tokens, capped at
+    min(ctx) - 1 (the token being decoded stays in every row's own tail) and
+    rounded down to a multiple of chunk_tokens; sharing below the first level
+    (a tree of prefixes) is not looked for. A group is one prefix item per R
+    members over [0, prefix_len) plus one item per member over
+    [prefix_len, ctx); every other row is one item over [0, ctx). So every
+    (row, chunk) below ctx is written by exactly one item, and the plan stays
+    valid while contexts only grow and new pages only join the tails."""
+    R = SP_MAX_COLS // G
+    ppc = chunk_tokens // page_size if chunk_tokens % page_size == 0 else 0
+    buckets = {}
+    for b, (pages, ctx) in enumerate(zip(page_lists, ctx_lens)):
+        if ppc and ctx > chunk_tokens and len(pages) >= ppc:
+            buckets.setdefault(tuple(pages[:ppc]), []).append(b)
+    items = []                              # (rows, t_begin, t_end)
+    grouped = set()
+    for rows in buckets.values():
+        if len(rows) < 2:
+            continue
+        run = 0
+        for col in zip(*(page_lists[b] for b in rows)):
+            if any(p != col[0] for p in col):
+                break
+            run += 1
+        prefix = min(run * page_size, min(ctx_lens[b] for b in rows) - 1)
+        prefix -= prefix % chunk_tokens
+        if prefix <= 0:
+            continue
+        grouped.update(rows)
+        for i in range(0, len(rows), R):
+            items.append((rows[i:i + R], 0, prefix))
+        items.extend(([b], prefix, -1) for b in rows)
+    if not grouped:
+        return None
+    items.extend(([b], 0, -1) for b in range(len(page_lists))
+                 if b not in grouped)
+    if len(items) > capacity:
+        raise ValueError(f"{len(items)} shared-prefix work items exceed the "
+                         f"capacity {capacity}")
+    item_rows = torch.full((capacity, R), -1, dtype=torch.int32)
+    item_range = torch.zeros(capacity, 2, dtype=torch.int32)
+    for w, (rows, t0, t1) in enumerate(items):
+        item_rows[w, :len(rows)] = torch.tensor(rows, dtype=torch.int32)
+        item_range[w, 0], item_range[w, 1] = t0, t1
+    return item_rows, item_range, max(len(it[0]) for it in items)
+
+
+def paged_attention_decode_shared(q, kcache, vcache, page_table, ctx_lens,
+                                  plan, scale,
+                                  scratch: "DecodeScratch | None" = None,
+                                  out=None):
+    """paged_attention_decode over d-major V pages with the work split of
+    `plan` = (item_rows, item_range, max_members) from shared_prefix_plan,
+    built with the scratch's chunk_tokens, on q's device. The plan changes
+    which block reads what, not the result."""
+    if q.is_cuda:
+        if out is None:
+            out = torch.empty_like(q)
+        assert scratch is not None, "GPU decode needs a DecodeScratch"
+        partial, ml = scratch.view(q.shape[0])
+        item_rows, item_range, max_members = plan
+        hip().paged_attention_decode_shared(
+            out, q, kcache, vcache, page_table, ctx_lens, item_rows,
+            item_range, partial, ml, scale, scratch.chunk_tokens, max_members)
+        return out
+    r = torch_ref.paged_attention_decode(q, kcache, vcache, page_table,
+                                         ctx_lens, scale, v_transposed=True)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
 def greedy_sample(logits: torch.Tensor, allow_fast: bool = True) -> torch.Tensor:
     if logits.is_cuda:
         out = torch.empty(logits.shape[0], dtype=torch.int32,

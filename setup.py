@@ -25,6 +25,7 @@ hip_sources = [
         "cache.hip",
         "attention_decode.hip",
         "attention_multiquery.hip",
+        "attention_shared_prefix.hip",
         "attention_prefill.hip",
         "skinny_gemm.hip",
         "quant_tile_gemm.hip",
