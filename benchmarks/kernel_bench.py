@@ -629,6 +629,101 @@ def bench_tile_sweep(Ms=(32, 48, 64, 96, 128, 256, 512), reps=3):
         del ws
 
 
+# MI355X dense peak of the fp8 MFMA (v_mfma_*_f8f6f4 with fp8 operands),
+# 2 x the bf16 MFMA's 2.5 PFLOP/s: the bound of the mx_gemm_sweep rows.
+MX_FP8_PEAK_TF = 5000.0
+
+
+def bench_mx_gemm_sweep(Ms=(256, 512, 1024, 2048, 4096, 8192), reps=3,
+                        shapes=None, acc_m=512):
+    """The W8A8 / W4A8 prefill GEMM (csrc/mx_gemm.hip) at every launchable
+    point on the four llama-3-70b layer shapes, cache-cold as bench_tile_sweep
+    is (launch i reads copy i % R of W, R * bytes(W) >= 1 GiB), against (1)
+    what the dispatch runs with the mx kernel switched off - dequantise + the
+    library GEMM (the tiled kernel at M = 256 if that is switched on), timed
+    as one unit - and (2) the bf16 dispatch. The new path's time includes the
+    activation quantiser. The candidates alternate inside each of `reps`
+    rounds; the figure is the minimum. At M = acc_m it also prints the
+    relative Frobenius error of the new path and of the parent path against
+    x.double() @ W_exact.T. Picks ops.*_MX_GEMM_SHAPES and MX_GEMM_MIN_M."""
+    from dynamo_amd.utils import enable_tunableop
+    enable_tunableop(tuning=False)
+    ops.set_mx_gemm(False)
+    for name, N, K in (("qkv", 10240, 8192), ("o", 8192, 8192),
+                       ("gateup", 57344, 8192), ("down", 8192, 28672)):
+        if shapes and name not in shapes:
+            continue
+        R = max(2, -(-(1 << 30) // (N * K * 2)))
+        ws = [torch.randn(N, K, dtype=torch.bfloat16, device="cuda") * 0.02
+              for _ in range(R)]
+        for fmt in ("fp8", "mxfp4"):
+            wbytes = N * K if fmt == "fp8" else N * K // 2 + N * K // 32
+            Rq = max(2, -(-(1 << 30) // wbytes))
+            holder = ops.Fp8Weight if fmt == "fp8" else ops.Mxfp4Weight
+            first = [holder.from_tensor(w) for w in ws]
+            hs = [first[r] if r < R else
+                  holder(first[r % R].q.clone(), first[r % R].scale.clone())
+                  for r in range(Rq)]
+            gemm = getattr(ops.hip(), f"{fmt}_mx_gemm")
+            for M in Ms:
+                x = torch.randn(M, K, dtype=torch.bfloat16, device="cuda")
+                y = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
+                xq = torch.empty(M, K, dtype=torch.float8_e4m3fn,
+                                 device="cuda")
+                xs = torch.empty(M, K // 32, dtype=torch.uint8, device="cuda")
+                i = [0]
+
+                def parent():
+                    i[0] += 1
+                    return ops.linear(x, hs[i[0] % Rq])
+
+                def bf16():
+                    i[0] += 1
+                    return ops.linear(x, ws[i[0] % R])
+
+                def mx(p):
+                    i[0] += 1
+                    h = hs[i[0] % Rq]
+                    ops.hip().mxfp8_quantize_rows(xq, xs, x)
+                    gemm(y, xq, xs, h.q, h.scale, *p)
+
+                path = (ops.fp8_linear_path if fmt == "fp8"
+                        else ops.mxfp4_linear_path)(x, hs[0])
+                cands = {f"parent:{path[0]}": parent, "bf16": bf16}
+                for p in ops.MX_GEMM_CONFIGS[fmt]:
+                    cands["mx:" + ",".join(map(str, p))] = (
+                        lambda p=p: mx(p))
+                iters = max(4, min(30, (1 << 15) // M))
+                ts = {c: [] for c in cands}
+                for _ in range(reps):
+                    for c, fn in cands.items():
+                        ts[c].append(timeit(fn, iters=iters, warmup=2))
+                t_parent = min(ts[f"parent:{path[0]}"])
+                for c, v in ts.items():
+                    t = min(v)
+                    tf = 2 * M * N * K / t / 1e12
+                    print(f"mx_gemm_sweep {fmt} {name} M={M} {c}: "
+                          f"{t*1e6:9.1f} us {tf:7.1f} TF "
+                          f"({100 * tf / MX_FP8_PEAK_TF:4.1f} % of the fp8 "
+                          f"MFMA peak) parent/this {t_parent/t:5.2f}",
+                          flush=True)
+                if M == acc_m:
+                    h = hs[0]
+                    wx = h.effective(torch.float32).double()
+                    ref = x.double() @ wx.T
+                    ops.hip().mxfp8_quantize_rows(xq, xs, x)
+                    gemm(y, xq, xs, h.q, h.scale, *ops.MX_GEMM_CONFIGS[fmt][0])
+                    e_new = ((y.double() - ref).norm() / ref.norm()).item()
+                    e_par = ((ops.linear(x, h).double() - ref).norm()
+                             / ref.norm()).item()
+                    print(f"mx_gemm_sweep {fmt} {name} M={M} relative "
+                          f"Frobenius error: mx {e_new:.3e} parent "
+                          f"{e_par:.3e}", flush=True)
+                    del wx, ref
+            del hs, first
+        del ws
+
+
 def _bench_fused_glu(label, fmt, cfg, y, gemm):
     """The gate/up GEMM with the SwiGLU epilogue against the unfused GEMM
     followed by silu_mul, both cache-cold the same way: gemm(out, r, glu)
@@ -1005,6 +1100,10 @@ if __name__ == "__main__":
         # launchable point per Mixtral shape: picks ops.MOE_TILE_MAX_T and
         # ops.MOE_TILE_SHAPES
         bench_moe_tiled_sweep()
+    if w == "mx_gemm_sweep":
+        # every launchable point of the W8A8 / W4A8 prefill GEMM per shape
+        # and M: picks ops.*_MX_GEMM_SHAPES and MX_GEMM_MIN_M
+        bench_mx_gemm_sweep()
     if w == "tile_sweep":
         # every launchable point of the tiled quantised GEMM per shape and M:
         # picks ops.*_TILE_GEMM_SHAPES, TILE_GEMM_MIN_M and TILE_GEMM_MAX_M

@@ -102,6 +102,16 @@ void mxfp4_tile_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor q,
                      int64_t nt, int64_t u, bool glu, int64_t nontemporal);
 std::map<std::string, std::vector<std::tuple<int, int, int, int, int>>>
 tile_gemm_configs();
+// mx_gemm.hip
+void mxfp8_quantize_rows(torch::Tensor xq, torch::Tensor xs, torch::Tensor x);
+void fp8_mx_gemm(torch::Tensor y, torch::Tensor xq, torch::Tensor xs,
+                 torch::Tensor wq, torch::Tensor scale, int64_t bm, int64_t bn,
+                 int64_t wm, int64_t wn, bool glu);
+void mxfp4_mx_gemm(torch::Tensor y, torch::Tensor xq, torch::Tensor xs,
+                   torch::Tensor q, torch::Tensor scale, int64_t bm,
+                   int64_t bn, int64_t wm, int64_t wn, bool glu);
+std::map<std::string, std::vector<std::tuple<int, int, int, int>>>
+mx_gemm_configs();
 // lora.hip
 void lora_shrink(torch::Tensor t, torch::Tensor x, torch::Tensor A_bank,
                  torch::Tensor slots, torch::Tensor ranks);
@@ -292,6 +302,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nontemporal") = -1);
   // {"fp8" | "mxfp4": [(BM, WN, WK, NT, U), ...]} they can launch
   m.def("tile_gemm_configs", &tile_gemm_configs);
+  // The W8A8 / W4A8 prefill GEMM on the block-scaled fp8/fp4 MFMA: x is
+  // quantised to MXFP8 rows (e4m3 xq [M, K], one e8m0 byte per 32 k in xs
+  // [M, K / 32], the bytes of ops.mxfp8.quantize_mxfp8_rows), then
+  // y = dq(xq, xs) @ W_eff^T at point (BM, BN, WM, WN) of mx_gemm_configs()
+  // for any M >= 1, N % 16 == 0, K % 128 == 0; raises on anything else
+  m.def("mxfp8_quantize_rows", &mxfp8_quantize_rows, py::arg("xq"),
+        py::arg("xs"), py::arg("x"));
+  m.def("fp8_mx_gemm", &fp8_mx_gemm, py::arg("y"), py::arg("xq"),
+        py::arg("xs"), py::arg("wq"), py::arg("scale"), py::arg("bm") = 128,
+        py::arg("bn") = 128, py::arg("wm") = 2, py::arg("wn") = 2,
+        py::arg("glu") = false);
+  m.def("mxfp4_mx_gemm", &mxfp4_mx_gemm, py::arg("y"), py::arg("xq"),
+        py::arg("xs"), py::arg("q"), py::arg("scale"), py::arg("bm") = 128,
+        py::arg("bn") = 128, py::arg("wm") = 2, py::arg("wn") = 2,
+        py::arg("glu") = false);
+  // {"fp8" | "mxfp4": [(BM, BN, WM, WN), ...]} they can launch
+  m.def("mx_gemm_configs", &mx_gemm_configs);
   // batched LoRA: each row i takes the adapter in bank slot slots[i] (a
   // device tensor; < 0 = none), so one captured graph serves any adapter mix.
   // t[i, r] = x[i] . A_bank[s, r] and y[i] += scales[s] * t[i] @ B_bank[s]^T

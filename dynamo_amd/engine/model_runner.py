@@ -113,6 +113,10 @@ class ModelRunner:
         elif self.weight_dtype == "mxfp4":
             # ValueError if a projection's K is no multiple of 32
             ops.quantize_model_mxfp4(self.model)
+        if (self.weight_dtype in ("fp8", "mxfp4")
+                and self.device.type == "cuda" and ops.mx_gemm_enabled()):
+            # the mx prefill GEMM's activation scratch, before any capture
+            ops.reserve_mx_scratch(self.model, cfg.max_batched_tokens)
         # the adapter bank too is allocated before the KV pool is sized
         self.lora_bank = None
         if cfg.max_loras > 0:

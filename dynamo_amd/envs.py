@@ -45,6 +45,13 @@ ENV_VARS = {
         "on the tiled W8A16 / W4A16 kernel (csrc/quant_tile_gemm.hip, x "
         "staged in LDS) up to ops.TILE_GEMM_MAX_M instead of dequantising "
         "the weight for the library GEMM. Default: off",
+    "DYNAMO_MX_GEMM":
+        "1 = fp8 / mxfp4 projection GEMMs at M >= ops.MX_GEMM_MIN_M (prefill "
+        "steps) quantise the activations to MXFP8 rows (e4m3, one e8m0 scale "
+        "per 32 k) and run on the block-scaled fp8/fp4 MFMA kernel "
+        "(csrc/mx_gemm.hip) instead of dequantising the weight for the bf16 "
+        "library GEMM. Changes the numbers: W8A8 / W4A8 above that M. "
+        "Default: off",
     "DYNAMO_MQ_ATTN":
         "1 = a step whose prefill part is runs of at most ops.MQ_MAX_Q query "
         "tokens per sequence (q_len * G <= ops.MQ_MAX_COLS, d-major V pages, "

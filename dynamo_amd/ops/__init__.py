@@ -8,11 +8,13 @@ from __future__ import annotations
 
 import torch
 
-from . import fp8_weights, mxfp4_weights, torch_ref
+from . import fp8_weights, mxfp4_weights, mxfp8, torch_ref
 from .fp8_weights import (Fp8ExpertWeight, Fp8Weight,  # re-export
                           quantize_fp8_rowwise, quantize_model_fp8)
 from .mxfp4_weights import (Mxfp4ExpertWeight, Mxfp4Weight,  # re-export
                             quantize_mxfp4, quantize_model_mxfp4)
+from .mxfp8 import (dequantize_mxfp8_rows,  # re-export
+                    quantize_mxfp8_rows)
 from .torch_ref import make_cos_sin_cache  # re-export
 
 _hip_mod = None
@@ -144,17 +146,23 @@ def _quant_gemm_config(M, N, K, kstep, max_m, shapes, split_k, default):
 
 
 def _quant_linear_path(x, w, dequant_k, gemm_config, fmt=None):
-    """("kernel", cfg) | ("tile", point) | ("dequant", None) | ("torch", None)
-    for linear(x, w) with a quantised weight holder w whose dequantise kernel
-    needs K % dequant_k == 0. fmt names the format's tiled kernel, asked
-    first where it is switched on (its MIN_M may lie below the skinny
-    kernel's largest M); None: the weight cannot take either kernel."""
+    """("kernel", cfg) | ("tile", point) | ("mx", point) | ("dequant", None) |
+    ("torch", None) for linear(x, w) with a quantised weight holder w whose
+    dequantise kernel needs K % dequant_k == 0. fmt names the format's mx and
+    tiled kernels, asked first (mx, then tiled) where they are switched on
+    (the tiled kernel's MIN_M may lie below the skinny kernel's largest M);
+    None: the weight can take none of the kernels."""
     N, K = w.shape
     if not x.is_cuda:
         return "torch", None
     if x.dtype != torch.bfloat16 or K % dequant_k or x.shape[-1] != K:
         return "torch", None
     if x.dim() == 2 and x.is_contiguous() and x.data_ptr() % 16 == 0:
+        if (fmt is not None and mx_gemm_enabled()
+                and w.q.data_ptr() % 16 == 0 and w.scale.data_ptr() % 4 == 0):
+            point = mx_gemm_config(fmt, x.shape[0], N, K)
+            if point is not None:
+                return "mx", point
         if fmt is not None and tile_gemm_enabled():
             point = tile_gemm_config(fmt, x.shape[0], N, K)
             if point is not None:
@@ -167,12 +175,19 @@ def _quant_linear_path(x, w, dequant_k, gemm_config, fmt=None):
 
 def _linear_quant(x, w, path, cfg, gemm: str, dequant: str, glu=False):
     """linear(x, w) on `path`; gemm and dequant name the format's bindings
-    (the tiled kernel's is the skinny one's with "tile" for "skinny").
-    glu (kernel and tile paths only): the fused SwiGLU form, y = [M, N / 2]."""
-    if path in ("kernel", "tile"):
+    (the tiled and mx kernels' are the skinny one's with "tile" / "mx" for
+    "skinny"). glu (kernel, tile and mx paths only): the fused SwiGLU form,
+    y = [M, N / 2]."""
+    if path in ("kernel", "tile", "mx"):
         y = torch.empty(x.shape[0], w.shape[0] // 2 if glu else w.shape[0],
                         dtype=x.dtype, device=x.device)
-        if path == "tile":
+        if path == "mx":
+            # x to MXFP8 rows in the device's scratch pair, then the GEMM
+            xq, xs = mxfp8.scratch_views(x.device, *x.shape)
+            hip().mxfp8_quantize_rows(xq, xs, x)
+            getattr(hip(), gemm.replace("_skinny_", "_mx_"))(
+                y, xq, xs, w.q, w.scale, *cfg, glu)
+        elif path == "tile":
             getattr(hip(), gemm.replace("_skinny_", "_tile_"))(
                 y, x, w.q, w.scale, *cfg, glu)
         else:
@@ -198,7 +213,9 @@ def fp8_linear_path(x: torch.Tensor, w: Fp8Weight):
     scratch buffer + the library GEMM, ("torch", None) for F.linear(x, W_eff)
     with W_eff formed by torch (CPU, or a GPU call fp8_dequant cannot
     serve). With the tiled kernel switched on (set_tile_gemm) also
-    ("tile", (BM, WN, WK, NT, U)) for fp8_tile_gemm."""
+    ("tile", (BM, WN, WK, NT, U)) for fp8_tile_gemm, with the mx kernel
+    switched on (set_mx_gemm) ("mx", (BM, BN, WM, WN)) for x quantised to
+    MXFP8 rows + fp8_mx_gemm."""
     return _quant_linear_path(x, w, 16, fp8_gemm_config, "fp8")
 
 
@@ -252,7 +269,9 @@ def mxfp4_linear_path(x: torch.Tensor, w: Mxfp4Weight):
     the scratch buffer + the library GEMM, ("torch", None) for
     F.linear(x, W_eff) with W_eff formed by torch (CPU, or x not bf16). With
     the tiled kernel switched on (set_tile_gemm) also
-    ("tile", (BM, WN, WK, NT, U)) for mxfp4_tile_gemm."""
+    ("tile", (BM, WN, WK, NT, U)) for mxfp4_tile_gemm, with the mx kernel
+    switched on (set_mx_gemm) ("mx", (BM, BN, WM, WN)) for x quantised to
+    MXFP8 rows + mxfp4_mx_gemm."""
     if w.q.data_ptr() % 16 or w.scale.data_ptr() % 8:
         return _quant_linear_path(x, w, 32, lambda M, N, K: None)
     return _quant_linear_path(x, w, 32, mxfp4_gemm_config, "mxfp4")
@@ -347,6 +366,94 @@ def tile_gemm_config(fmt: str, M: int, N: int, K: int):
     return point
 
 
+# --------------------------------------------------------------------------
+# W8A8 / W4A8 prefill GEMM (csrc/mx_gemm.hip): above the tiled kernel's M the
+# activations are quantised to MXFP8 rows (ops/mxfp8.py) and the product runs
+# on the block-scaled fp8 x fp8 / fp8 x fp4 MFMA instead of dequantising the
+# weight for the bf16 library GEMM. A numerical change (x loses precision),
+# so opt-in (DYNAMO_MX_GEMM=1 / set_mx_gemm): off, every call runs where it
+# ran before. (BM, BN, WM, WN) points the bindings can launch, a copy of the
+# kernel file's table that tests can read without the extension; they check
+# it against hip().mx_gemm_configs(). Every point accepts every K % 128 == 0
+# and has a GLU form.
+MX_GEMM_POINTS: tuple = (
+    (128, 128, 2, 2), (256, 128, 2, 2), (256, 128, 4, 2), (128, 256, 2, 2),
+)
+MX_GEMM_CONFIGS: dict = {"fp8": MX_GEMM_POINTS, "mxfp4": MX_GEMM_POINTS}
+MX_GEMM_KSTEP = 128
+# (N, K) -> ((largest M, point), ...) with M ascending, for the llama-3-70b
+# layer shapes (kernel_bench.py --which mx_gemm_sweep; profiles/README.md,
+# "MX GEMM"): an M range is listed only where quantise + mx GEMM beat
+# dequantise + library GEMM in both of two sweeps by more than the runs
+# differ, and a listed shape above its last M stays on the dequantise path.
+# qkv and o won at no measured M above 256 and are listed empty.
+FP8_MX_GEMM_SHAPES: dict = {
+    (10240, 8192): (),                                              # qkv
+    (8192, 8192): (),                                               # o
+    (57344, 8192): ((512, (256, 128, 4, 2)), (1024, (128, 128, 2, 2))),
+    (8192, 28672): ((512, (128, 128, 2, 2)), (1024, (128, 256, 2, 2))),
+}
+MXFP4_MX_GEMM_SHAPES: dict = {
+    (10240, 8192): (),                                              # qkv
+    (8192, 8192): (),                                               # o
+    (57344, 8192): ((512, (128, 128, 2, 2)),),                      # gate/up
+    (8192, 28672): ((512, (128, 128, 2, 2)),),                      # down
+}
+MX_GEMM_SHAPES: dict = {"fp8": FP8_MX_GEMM_SHAPES,
+                        "mxfp4": MXFP4_MX_GEMM_SHAPES}
+# The M a shape outside the table takes the mx path at, on the first point.
+# MIN_M: the tiled kernel's largest M + 1. MAX_M: the largest measured M at
+# which the mx path was ahead on gate/up and down; above it the kernel (0.9 -
+# 1.15 PFLOP/s) is behind the library GEMM on every measured shape.
+MX_GEMM_MIN_M: dict = {"fp8": 257, "mxfp4": 257}
+MX_GEMM_MAX_M: dict = {"fp8": 1024, "mxfp4": 512}
+
+_mx_gemm_override: "bool | None" = None
+
+
+def set_mx_gemm(on: "bool | None") -> None:
+    """In-process override of DYNAMO_MX_GEMM (None = follow the env)."""
+    global _mx_gemm_override
+    _mx_gemm_override = on
+
+
+def mx_gemm_enabled() -> bool:
+    if _mx_gemm_override is not None:
+        return _mx_gemm_override
+    from dynamo_amd import envs
+    return envs.get("DYNAMO_MX_GEMM", False, bool)
+
+
+def mx_gemm_config(fmt: str, M: int, N: int, K: int):
+    """The (BM, BN, WM, WN) the mx kernel of fmt ("fp8" | "mxfp4") runs an
+    [M, K] x [N, K]^T call at, or None if it does not take the call: M below
+    MX_GEMM_MIN_M, above the shape's last table entry (MX_GEMM_MAX_M for a
+    shape outside the table) or a shape the kernel cannot do. The switch is
+    the caller's business."""
+    if not (M >= MX_GEMM_MIN_M[fmt] and K >= MX_GEMM_KSTEP
+            and K % MX_GEMM_KSTEP == 0 and N >= 16 and N % 16 == 0):
+        return None
+    entries = MX_GEMM_SHAPES[fmt].get((N, K))
+    if entries is None:
+        return (MX_GEMM_CONFIGS[fmt][0] if M <= MX_GEMM_MAX_M[fmt] else None)
+    for max_m, p in entries:
+        if M <= max_m:
+            return p
+    return None
+
+
+def reserve_mx_scratch(model, tokens: int) -> None:
+    """Size the MXFP8 scratch pair of the model's device for a step of
+    `tokens` tokens: tokens x the largest K of its quantised dense
+    projections. The model runner calls this before any graph capture when
+    the mx path is switched on."""
+    for layer in model.layers:
+        for sub, name in fp8_weights.PROJECTIONS:
+            w = getattr(getattr(layer, sub, None), name, None)
+            if isinstance(w, (Fp8Weight, Mxfp4Weight)):
+                mxfp8.reserve_scratch(w.device, tokens * w.shape[1])
+
+
 def linear(x: torch.Tensor, w) -> torch.Tensor:
     """x @ w^T. Decode-regime calls (M <= 16) on a shipped (N, K) take the
     in-tree weight-streaming kernel; every other call is F.linear. An
@@ -417,6 +524,9 @@ def fused_glu_config(x: torch.Tensor, w):
         if path == "tile":   # every point of the tiled kernel has a GLU form
             return ((f"{fmt}_tile_gemm", cfg) if fmt in FUSED_GLU_FORMATS
                     and cfg[3] % 2 == 0 else None)
+        if path == "mx":     # every point of the mx kernel has one too
+            return ((f"{fmt}_mx_gemm", cfg) if fmt in FUSED_GLU_FORMATS
+                    else None)
         hit = (f"{fmt}_skinny_gemm", fmt, cfg) if path == "kernel" else None
     else:
         cfg = skinny_gemm_config(x, w)
@@ -437,8 +547,10 @@ def linear_silu_mul(x: torch.Tensor, w_gate_up) -> torch.Tensor:
         return silu_mul(linear(x, w_gate_up))
     gemm, cfg = hit
     if gemm != "skinny_gemm":
-        path = "tile" if gemm.endswith("_tile_gemm") else "kernel"
-        return _linear_quant(x, w_gate_up, path, cfg, gemm, None, True)
+        path = ("tile" if gemm.endswith("_tile_gemm") else
+                "mx" if gemm.endswith("_mx_gemm") else "kernel")
+        return _linear_quant(x, w_gate_up, path, cfg,
+                             gemm.replace("_mx_", "_skinny_"), None, True)
     y = torch.empty(x.shape[0], w_gate_up.shape[0] // 2, dtype=x.dtype,
                     device=x.device)
     hip().skinny_gemm(y, x, w_gate_up, *cfg, True)

@@ -29,6 +29,7 @@ hip_sources = [
         "attention_prefill.hip",
         "skinny_gemm.hip",
         "quant_tile_gemm.hip",
+        "mx_gemm.hip",
         "sampling.hip",
         "logits_process.hip",
         "moe.hip",
