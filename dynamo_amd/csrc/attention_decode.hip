@@ -156,3 +156,100 @@ void paged_attention_decode(torch::Tensor out, torch::Tensor q,
     HIP_CHECK_KERNEL();
   }
 }
+
+// rope_append_qkv(v_transposed) + paged_attention_decode(v_transposed) of one
+// decode step in one phase-1 kernel (see RopeAppendArgs): row b of qkv is the
+// new token of sequence b, slot_mapping[b] the slot of token ctx_lens[b] - 1
+// under page_table[b] or negative (a padded row: nothing is appended). bf16
+// d-major V pages only; everything else takes the two kernels.
+void paged_attention_decode_rope(
+    torch::Tensor out, torch::Tensor qkv, c10::optional<torch::Tensor> bias,
+    torch::Tensor positions, torch::Tensor slot_mapping,
+    torch::Tensor cos_sin_cache, torch::Tensor kcache, torch::Tensor vcache,
+    torch::Tensor page_table, torch::Tensor ctx_lens, torch::Tensor partial,
+    torch::Tensor ml, double scale, int64_t chunk_tokens, int64_t nt_policy) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.dtype() == torch::kBFloat16);
+  TORCH_CHECK(qkv.dim() == 2 && qkv.stride(1) == 1);
+  TORCH_CHECK(out.dim() == 3 && out.is_contiguous() &&
+              out.dtype() == torch::kBFloat16);
+  TORCH_CHECK(kcache.dtype() == torch::kBFloat16 &&
+                  vcache.dtype() == torch::kBFloat16,
+              "the fused rope-append decode needs a bf16 kv cache");
+  TORCH_CHECK(page_table.dtype() == torch::kInt32 &&
+              ctx_lens.dtype() == torch::kInt32 &&
+              positions.dtype() == torch::kInt32 &&
+              slot_mapping.dtype() == torch::kInt64 &&
+              cos_sin_cache.dtype() == torch::kFloat32);
+  const int B = out.size(0);
+  const int Hq = out.size(1);
+  const int hd = out.size(2);
+  const int Hkv = kcache.size(1);
+  const int ps = kcache.size(2);
+  const int G = Hq / Hkv;
+  const int max_pages = page_table.size(1);
+  const int C = ml.size(2);
+  TORCH_CHECK(hd == 128 && kcache.size(3) == hd, "only head_dim=128");
+  TORCH_CHECK(partial.dim() == 4 && ml.dim() == 4 && partial.size(0) >= B &&
+              ml.size(0) >= B && partial.size(1) == Hq && ml.size(1) == Hq &&
+              partial.size(2) == C && partial.size(3) == hd &&
+              partial.is_contiguous() && ml.is_contiguous());
+  TORCH_CHECK((ps & (ps - 1)) == 0 && ps % 32 == 0,
+              "page_size must be a power of 2 and a multiple of 32");
+  TORCH_CHECK(Hq == G * Hkv && G >= 2 && G <= 16, "needs 2<=G<=16, got ", G);
+  TORCH_CHECK(vcache.size(2) == hd && vcache.size(3) == ps,
+              "expects d-major V pages: vcache [P, Hkv, hd, ps]");
+  TORCH_CHECK(kcache.is_contiguous() && vcache.is_contiguous() &&
+              page_table.is_contiguous() && cos_sin_cache.is_contiguous());
+  TORCH_CHECK(cos_sin_cache.dim() == 2 && cos_sin_cache.size(1) == hd);
+  // 16-byte vector loads of the qkv rows and the bias
+  TORCH_CHECK(qkv.size(0) >= B && qkv.size(1) >= (Hq + 2 * Hkv) * hd &&
+              qkv.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0);
+  TORCH_CHECK(positions.numel() >= B && slot_mapping.numel() >= B &&
+              ctx_lens.numel() >= B && page_table.size(0) >= B &&
+              positions.is_contiguous() && slot_mapping.is_contiguous());
+  const short* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->numel() == (Hq + 2 * Hkv) * hd &&
+                bias->dtype() == torch::kBFloat16 && bias->is_contiguous());
+    bp = (const short*)bias->data_ptr();
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(bp) % 16 == 0);
+  }
+  int log2_ps = 0; while ((1 << log2_ps) < ps) log2_ps++;
+  if (B == 0) return;
+  const int chunk = (int)chunk_tokens;
+  TORCH_CHECK(chunk >= 128 && chunk % 128 == 0, "bad chunk_tokens ", chunk);
+  auto stream = at::cuda::getCurrentHIPStream();
+  static const bool nt_env = [] {
+    const char* e = getenv("DYNAMO_DECODE_NT");
+    return e == nullptr ? kDecodeNtDefault : e[0] != '0';
+  }();
+  const bool use_nt = nt_policy < 0 ? nt_env : nt_policy != 0;
+  const RopeAppendArgs ra{
+      (const short*)qkv.data_ptr(), bp, positions.data_ptr<int32_t>(),
+      slot_mapping.data_ptr<int64_t>(), cos_sin_cache.data_ptr<float>(),
+      (short*)kcache.data_ptr(), (short*)vcache.data_ptr(),
+      (int)qkv.stride(0)};
+  const int lds = mfma_swapped_lds_bytes(G, hd);
+  auto launch = [&](auto* kern) {
+    if (lds > 65536)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                lds);
+    kern<<<dim3(B, Hkv, C), kBlock, lds, stream>>>(
+        partial.data_ptr<float>(), ml.data_ptr<float>(),
+        (short*)out.data_ptr(), (const short*)kcache.data_ptr(),
+        (const short*)vcache.data_ptr(), page_table.data_ptr<int32_t>(),
+        ctx_lens.data_ptr<int32_t>(), (float)scale, chunk, G, B, Hkv, C,
+        max_pages, log2_ps, hd, ra);
+  };
+  if (use_nt) launch(&paged_decode_mfma_swapped_dmajor_rope<1>);
+  else launch(&paged_decode_mfma_swapped_dmajor_rope<0>);
+  HIP_CHECK_KERNEL();
+  if (C > 1) {
+    paged_decode_phase2<<<dim3(B, Hq), 128, 0, stream>>>(
+        (short*)out.data_ptr(), partial.data_ptr<float>(), ml.data_ptr<float>(),
+        ctx_lens.data_ptr<int32_t>(), chunk, Hq, C, hd);
+    HIP_CHECK_KERNEL();
+  }
+}

@@ -8,12 +8,16 @@
 //                                  the DYNAMO_DECODE_SWAPPED=0 fallback
 //   paged_decode_mfma_swapped      MFMA, tokens on the M rows, token-major V
 //   paged_decode_mfma_swapped_dmajor   the same with d-major ("VT4") V pages
+//   paged_decode_mfma_swapped_dmajor_rope   the same body taking the qkv
+//                                  GEMM rows: ropes q and appends the new
+//                                  token's k / v itself (bf16 pages)
 // The pieces they have in common (empty-chunk exit, Q staging, K/V slice
 // load, P pack, cross-wave merge + store) are the helpers below. The
 // measured history of the variants that did not ship is in
 // profiles/README.md.
 #pragma once
 #include "common.h"
+#include "rope_impl.h"
 #include <cstdlib>
 
 namespace decode_attn {
@@ -52,7 +56,7 @@ constexpr float kDeferMax = 8.0f;
 // == 0) and every b64 staging write is ~16-way conflicted; 72 puts them 16
 // banks apart (8 * 18 % 32 == 16), halving the conflicts with less LDS than
 // 88. The d-major kernel stages K in the same per-wave region and uses
-// 8 KB of its 9 KB.
+// 8 KB of its 9 KB (its rope form 512 B more, for the new token's k and v).
 constexpr int kVStride = 72;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -904,23 +908,57 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma_swapped(
 //   the region the token-major kernel stages V in). Two 32-token halves
 //   reuse the buffer; wave-local barriers only.
 // NT selects non-temporal K and V loads (see ld8).
-template <int FP8, int NT>
-__global__ __launch_bounds__(kBlock) void paged_decode_mfma_swapped_dmajor(
+//
+// ROPE = 1 (paged_decode_mfma_swapped_dmajor_rope, bf16 pages only) folds
+// rope_append_unit_kernel<0, 1> into this kernel: it takes the raw qkv GEMM
+// rows instead of a roped q. Every block ropes its own G query heads into
+// q_lds_s, and the ONE wave of the (b, h) blocks whose slab holds token
+// ctx - 1 ropes that token's k, takes its v, writes both to the pages at
+// slot_mapping[b] (the bytes the unit kernel writes; nothing for a negative
+// slot) and parks them in the spare 1 KB of its LDS region. From there it
+// patches the staged K row and the PV A-fragment element of that token, so
+// nothing it wrote is read back from global memory: no other wave of the
+// grid reads token ctx - 1, hence no fence and no hand-off. The caller
+// guarantees what the engine's decode step does: slot_mapping[b] is the slot
+// of token ctx_lens[b] - 1 under page_table[b], or negative (then the token
+// is read from the pages like every other one).
+struct RopeAppendArgs {
+  const short* qkv;           // [B, row_stride] (q | k | v per row)
+  const short* bias;          // [(Hq + 2 Hkv) * hd] or null
+  const int32_t* positions;   // [B]
+  const int64_t* slots;       // [B]
+  const float* cos_sin;       // [max_pos, hd] (cos half, sin half)
+  short* kcache;              // the pages again, writable
+  short* vcache;
+  int row_stride;
+};
+
+template <int FP8, int NT, int ROPE>
+__device__ __forceinline__ void dmajor_decode_body(
     float* __restrict__ partial, float* __restrict__ ml,
     short* __restrict__ out, const short* __restrict__ q,
-    const short* __restrict__ kcache, const short* __restrict__ vcache,
+    const short* kcache, const short* vcache,
     const int32_t* __restrict__ page_table, const int32_t* __restrict__ ctx_lens,
     float scale, int chunk, int G, int B, int Hkv, int C, int max_pages,
-    int log2_ps, int hd) {
+    int log2_ps, int hd, const RopeAppendArgs& ra) {
+  static_assert(!(ROPE && FP8), "the fused rope-append writes bf16 pages");
   const int kSlab = chunk / 4;
   const int b = blockIdx.x;
   const int h = blockIdx.y;
   const int c = blockIdx.z;
   const int Hq = Hkv * G;
   const int ctx = ctx_lens[b];
+  // ROPE: asked for beside ctx, so the cos/sin loads that wait for the
+  // position go out with the qkv loads and cost no round trip of their own
+  const int pos = ROPE ? ra.positions[b] : 0;
+  const int64_t slot = ROPE ? ra.slots[b] : -1;
   const int chunk_start = c * chunk;
   const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
+  // ROPE: the wave index as a scalar keeps the slab bounds and the LDS base
+  // in SGPRs, which pays for the prologue and the two patches (202 VGPRs
+  // against 214 with the plain form, 2 waves per SIMD against 1)
+  const int wid = ROPE ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)
+                       : (int)(threadIdx.x >> 6);
   const int lr = lane & 15;
   const int lg = lane >> 4;
   const int ps = 1 << log2_ps;
@@ -929,23 +967,20 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma_swapped_dmajor(
   float* merge = lds;                                   // 4*G*(hd+2)
   short* q_lds_s = reinterpret_cast<short*>(merge + 4 * G * (hd + 2));
   short* k_lds = q_lds_s + G * hd + wid * (hd * kVStride / 2);  // per-wave
+  // ROPE: the new token's k and v rows (256 B each) behind the 8 KB K stage
+  short* k_new = k_lds + 4096;
+  short* v_new = k_new + 128;
 
   if (chunk_start >= ctx) {
     write_empty_chunk(ml, out, b, h, c, G, Hq, C, hd);
     return;
   }
-  stage_q(q_lds_s, q, b, h, G, Hq, hd);
-  bf16x8_t q_frag[4];
-  load_q_frag(q_frag, q_lds_s, G, hd, lr, lg);
-
-  float m_run = kNegInf, l_run = 0.f;
-  f32x4 acc[8];
-#pragma unroll
-  for (int d = 0; d < 8; d++) acc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int slab_start = chunk_start + wid * kSlab;
   const int slab_end = min(slab_start + kSlab, ctx);
   const int32_t* pt = page_table + (int64_t)b * max_pages;
+  // ROPE: the token this wave appends (wave-uniform), -1 = none
+  int tn = -1;
 
   // 32 tokens of K -> LDS [32 rows][256 B], 16 B chunks XOR-swizzled by
   // row. Burst i covers rows {i*4 .. i*4+3} fully (lane>>4 = row, lane&15
@@ -968,9 +1003,110 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma_swapped_dmajor(
           (char*)k_lds + row * 256 +
           (((lane & 15) * 16) ^ ((row & 7) << 4))) = sreg[i];
     }
+    if constexpr (ROPE) {
+      // the new token's row was loaded stale: overwrite it with the roped k
+      // (one wave's LDS writes land in issue order)
+      if (tn >= tb32 && tn < tb32 + 32) {
+        const int row = tn - tb32;
+        if (lane < 16)
+          *reinterpret_cast<short8*>(
+              (char*)k_lds + row * 256 + ((lane * 16) ^ ((row & 7) << 4))) =
+              *reinterpret_cast<const short8*>(k_new + lane * 8);
+      }
+    }
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
+
+  short8 v64[16], sreg[8];
+  if constexpr (ROPE) {
+    const int half = hd / 2;
+    const int upr = hd / 16;                  // rope units per head
+    const int i0 = (lane % upr) * 8;          // upr divides the wave
+    const short* row = ra.qkv + (int64_t)b * ra.row_stride;
+    if (slot >= 0 && slab_start < ctx && ctx <= slab_start + kSlab)
+      tn = ctx - 1;
+    // wave-uniform by construction; say so, so that the patches in the tile
+    // loop are scalar branches and tn costs no VGPR
+    tn = __builtin_amdgcn_readfirstlane(tn);
+    // q: one unit per thread of the first G * upr; k: lanes 0 .. upr-1 and
+    // v: lanes 16 .. 16 + hd/8 - 1 of the appending wave
+    const bool qunit = (int)threadIdx.x < G * upr;
+    const bool kunit = tn >= 0 && lane < upr;
+    const bool vunit = tn >= 0 && lane >= 16 && lane < 16 + hd / 8;
+    const int qoff = (h * G + (int)threadIdx.x / upr) * hd;
+    const int koff = (Hq + h) * hd;
+    const int voff = (Hq + Hkv + h) * hd + (lane - 16) * 8;
+    short8 x1{}, x2{}, b1{}, b2{}, kx1{}, kx2{}, kb1{}, kb2{}, vv{}, vb{};
+    if (qunit) {
+      x1 = *reinterpret_cast<const short8*>(row + qoff + i0);
+      x2 = *reinterpret_cast<const short8*>(row + qoff + half + i0);
+      if (ra.bias) {
+        b1 = *reinterpret_cast<const short8*>(ra.bias + qoff + i0);
+        b2 = *reinterpret_cast<const short8*>(ra.bias + qoff + half + i0);
+      }
+    }
+    if (kunit) {
+      kx1 = *reinterpret_cast<const short8*>(row + koff + i0);
+      kx2 = *reinterpret_cast<const short8*>(row + koff + half + i0);
+      if (ra.bias) {
+        kb1 = *reinterpret_cast<const short8*>(ra.bias + koff + i0);
+        kb2 = *reinterpret_cast<const short8*>(ra.bias + koff + half + i0);
+      }
+    }
+    if (vunit) {
+      vv = *reinterpret_cast<const short8*>(row + voff);
+      if (ra.bias) vb = *reinterpret_cast<const short8*>(ra.bias + voff);
+    }
+    float4v c0{}, c1{}, s0{}, s1{};
+    if (qunit || kunit) {
+      const float* cs = ra.cos_sin + (int64_t)pos * hd;
+      c0 = *reinterpret_cast<const float4v*>(cs + i0);
+      c1 = *reinterpret_cast<const float4v*>(cs + i0 + 4);
+      s0 = *reinterpret_cast<const float4v*>(cs + half + i0);
+      s1 = *reinterpret_cast<const float4v*>(cs + half + i0 + 4);
+    }
+    if (qunit) {
+      short8 o1, o2;
+      rope::rotate8(x1, x2, ra.bias != nullptr, b1, b2, c0, c1, s0, s1, o1,
+                    o2);
+      short* qd = q_lds_s + ((int)threadIdx.x / upr) * hd;
+      *reinterpret_cast<short8*>(qd + i0) = o1;
+      *reinterpret_cast<short8*>(qd + half + i0) = o2;
+    }
+    if (kunit) {
+      short8 o1, o2;
+      rope::rotate8(kx1, kx2, ra.bias != nullptr, kb1, kb2, c0, c1, s0, s1,
+                    o1, o2);
+      const int64_t kb =
+          (((slot >> log2_ps) * Hkv + h) * ps + (slot & (ps - 1))) * hd;
+      *reinterpret_cast<short8*>(ra.kcache + kb + i0) = o1;
+      *reinterpret_cast<short8*>(ra.kcache + kb + half + i0) = o2;
+      *reinterpret_cast<short8*>(k_new + i0) = o1;
+      *reinterpret_cast<short8*>(k_new + half + i0) = o2;
+    }
+    if (vunit) {
+      if (ra.bias) vv = rope::add_bias8(vv, vb);
+      const int d = (lane - 16) * 8;
+      // d-major page: elem offset d * ps + token_in_page
+      const int64_t vb0 =
+          (((slot >> log2_ps) * Hkv + h) * hd + d) * ps + (slot & (ps - 1));
+#pragma unroll
+      for (int e = 0; e < 8; e++) ra.vcache[vb0 + (int64_t)e * ps] = vv[e];
+      *reinterpret_cast<short8*>(v_new + d) = vv;
+    }
+    __syncthreads();   // q_lds_s to the block; k_new / v_new to the wave
+  } else {
+    stage_q(q_lds_s, q, b, h, G, Hq, hd);
+  }
+  bf16x8_t q_frag[4];
+  load_q_frag(q_frag, q_lds_s, G, hd, lr, lg);
+
+  float m_run = kNegInf, l_run = 0.f;
+  f32x4 acc[8];
+#pragma unroll
+  for (int d = 0; d < 8; d++) acc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+
   // S^T tiles 2*half and 2*half+1 of the 64-token tile from the staged K
   auto qk_half = [&](int t0, int half, f32x4 (&sT)[4]) {
     __builtin_amdgcn_s_setprio(1);
@@ -1022,6 +1158,18 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma_swapped_dmajor(
             if (lg * 8 + j >= rem) v8[j] = 0;
         }
         vf[da * 2 + tc] = v8;
+      }
+      if constexpr (ROPE) {
+        // the new token's element of its 8-token run was loaded stale
+        if (tn >= tb && tn < tb + 32 && lg == ((tn - tb) >> 3)) {
+#pragma unroll
+          for (int da = 0; da < 8; da++) {
+            const short nv = v_new[da * 16 + lr];
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+              if (j == (tn & 7)) vf[da * 2 + tc][j] = nv;
+          }
+        }
       }
     }
   };
@@ -1085,7 +1233,6 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma_swapped_dmajor(
     __builtin_amdgcn_s_setprio(0);
   };
 
-  short8 v64[16], sreg[8];
   for (int t0 = slab_start; t0 < slab_end; t0 += 64) {
     f32x4 sT[4];
     stage_k32(t0, sreg);          // K half A (tokens t0..t0+31)
@@ -1102,6 +1249,32 @@ __global__ __launch_bounds__(kBlock) void paged_decode_mfma_swapped_dmajor(
 
   swapped_merge_store(merge, acc, m_run, l_run, partial, ml, out, b, h, c, G,
                       Hq, C, hd, wid, lr, lg);
+}
+
+template <int FP8, int NT>
+__global__ __launch_bounds__(kBlock) void paged_decode_mfma_swapped_dmajor(
+    float* __restrict__ partial, float* __restrict__ ml,
+    short* __restrict__ out, const short* __restrict__ q,
+    const short* __restrict__ kcache, const short* __restrict__ vcache,
+    const int32_t* __restrict__ page_table, const int32_t* __restrict__ ctx_lens,
+    float scale, int chunk, int G, int B, int Hkv, int C, int max_pages,
+    int log2_ps, int hd) {
+  dmajor_decode_body<FP8, NT, 0>(partial, ml, out, q, kcache, vcache,
+                                 page_table, ctx_lens, scale, chunk, G, B, Hkv,
+                                 C, max_pages, log2_ps, hd, RopeAppendArgs{});
+}
+
+// The caches are not __restrict__ here: ra names them again for the append.
+template <int NT>
+__global__ __launch_bounds__(kBlock) void paged_decode_mfma_swapped_dmajor_rope(
+    float* __restrict__ partial, float* __restrict__ ml,
+    short* __restrict__ out, const short* kcache, const short* vcache,
+    const int32_t* __restrict__ page_table, const int32_t* __restrict__ ctx_lens,
+    float scale, int chunk, int G, int B, int Hkv, int C, int max_pages,
+    int log2_ps, int hd, RopeAppendArgs ra) {
+  dmajor_decode_body<0, NT, 1>(partial, ml, out, nullptr, kcache, vcache,
+                               page_table, ctx_lens, scale, chunk, G, B, Hkv,
+                               C, max_pages, log2_ps, hd, ra);
 }
 
 inline int mfma_swapped_lds_bytes(int G, int hd) {

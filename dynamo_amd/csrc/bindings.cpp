@@ -38,6 +38,12 @@ void paged_attention_decode(torch::Tensor out, torch::Tensor q, torch::Tensor kc
                             torch::Tensor ml, double scale,
                             int64_t chunk_tokens, bool v_transposed,
                             int64_t nt_policy);
+void paged_attention_decode_rope(
+    torch::Tensor out, torch::Tensor qkv, c10::optional<torch::Tensor> bias,
+    torch::Tensor positions, torch::Tensor slot_mapping,
+    torch::Tensor cos_sin_cache, torch::Tensor kcache, torch::Tensor vcache,
+    torch::Tensor page_table, torch::Tensor ctx_lens, torch::Tensor partial,
+    torch::Tensor ml, double scale, int64_t chunk_tokens, int64_t nt_policy);
 // attention_multiquery.hip
 void paged_attention_multiquery(
     torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
@@ -210,6 +216,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("page_table"), py::arg("ctx_lens"), py::arg("partial"),
         py::arg("ml"), py::arg("scale"), py::arg("chunk_tokens"),
         py::arg("v_transposed") = false, py::arg("nt_policy") = -1);
+  // one decode step's rope_append_qkv + paged_attention_decode in one
+  // phase-1 kernel (bf16 d-major V pages): takes the qkv GEMM rows, ropes q
+  // in the kernel and appends token ctx_lens[b] - 1 at slot_mapping[b]
+  m.def("paged_attention_decode_rope", &paged_attention_decode_rope,
+        py::arg("out"), py::arg("qkv"), py::arg("bias"), py::arg("positions"),
+        py::arg("slot_mapping"), py::arg("cos_sin"), py::arg("kcache"),
+        py::arg("vcache"), py::arg("page_table"), py::arg("ctx_lens"),
+        py::arg("partial"), py::arg("ml"), py::arg("scale"),
+        py::arg("chunk_tokens"), py::arg("nt_policy") = -1);
   // 2..8 query tokens per sequence on a long context, split over the
   // context like decode (d-major V pages, hd 128, q_len * G <= 64);
   // row_ctx[Tq] is the causal limit of every flattened q row

@@ -3,7 +3,7 @@
 // cos/sin are precomputed on host into a [max_pos, rot_dim] fp32 table
 // (first half cos, second half sin) per guide Appendix B: on-device trig
 // turns a memory-bound op VALU-bound. Vectorized 8-wide bf16 loads.
-#include "common.h"
+#include "rope_impl.h"
 #include <hip/hip_fp8.h>
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -227,18 +227,25 @@ __global__ __launch_bounds__(kBlock) void rope_append_unit_kernel(
     float4v s1 = *reinterpret_cast<const float4v*>(cs + half + i0 + 4);
     const int64_t slot = slots[t];
     short8 o1, o2;
+    if constexpr (FP8) {
+      // The fp8 instantiations of both kernels have always been contracted
+      // the other way round (see rope::rotate8) and agree with each other;
+      // their expression stays here, as the compiler has always seen it.
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const float c = (i < 4) ? c0[i] : c1[i - 4];
-      const float s = (i < 4) ? s0[i] : s1[i - 4];
-      float a = bf16_to_f32(x1[i]);
-      float b = bf16_to_f32(x2[i]);
-      if (bias) {
-        a += bf16_to_f32(b1[i]);
-        b += bf16_to_f32(b2[i]);
+      for (int i = 0; i < 8; i++) {
+        const float c = (i < 4) ? c0[i] : c1[i - 4];
+        const float s = (i < 4) ? s0[i] : s1[i - 4];
+        float a = bf16_to_f32(x1[i]);
+        float b = bf16_to_f32(x2[i]);
+        if (bias) {
+          a += bf16_to_f32(b1[i]);
+          b += bf16_to_f32(b2[i]);
+        }
+        o1[i] = f32_to_bf16(a * c - b * s);
+        o2[i] = f32_to_bf16(b * c + a * s);
       }
-      o1[i] = f32_to_bf16(a * c - b * s);
-      o2[i] = f32_to_bf16(b * c + a * s);
+    } else {
+      rope::rotate8(x1, x2, bias != nullptr, b1, b2, c0, c1, s0, s1, o1, o2);
     }
     if (h < Hq) {
       short* qb = q_out + ((int64_t)t * Hq + h) * hd;
@@ -282,11 +289,7 @@ __global__ __launch_bounds__(kBlock) void rope_append_unit_kernel(
   if (slot < 0) return;
   const int64_t page = slot / page_size;
   const int off = (int)(slot % page_size);
-  if (bias) {
-#pragma unroll
-    for (int e = 0; e < 8; e++)
-      v[e] = f32_to_bf16(bf16_to_f32(v[e]) + bf16_to_f32(bv[e]));
-  }
+  if (bias) v = rope::add_bias8(v, bv);
   if constexpr (VT) {
     // transposed page: elem offset d * ps + token_in_page
     const int64_t vb0 = ((page * Hkv + h) * hd + d) * page_size + off;

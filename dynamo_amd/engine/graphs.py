@@ -77,6 +77,7 @@ class GraphRunner:
             shared = (*self.shared_items[bc], has_shared * 16 // G)
         return AttnMetadata(
             decode_shared=shared,
+            decode_step=True,
             lora_slots=self.lora_slots[:bc] if has_lora else None,
             lora_decode_rows=bc if has_lora else 0,
             slot_mapping=self.slot_mapping[:bc],

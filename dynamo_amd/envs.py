@@ -33,6 +33,11 @@ ENV_VARS = {
     "DYNAMO_DECODE_NT":
         "1 = non-temporal K/V loads in the d-major (VT4) decode attention "
         "kernel (bit-identical outputs; recorded-negative, slower)",
+    "DYNAMO_FUSED_ROPE_ATTN":
+        "0 = a decode step runs rope_append_qkv and decode attention as two "
+        "kernels (default: on bf16 d-major V pages the d-major decode kernel "
+        "ropes q and appends the new token's k / v itself where "
+        "ops.fused_rope_attn_ready allows; equal bits either way)",
     "DYNAMO_SKINNY_GEMM":
         "0 = every decode weight GEMM on hipBLASLt (default: the in-tree "
         "skinny-M kernel on the shapes in ops.SKINNY_GEMM_SHAPES)",

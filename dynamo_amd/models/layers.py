@@ -34,6 +34,11 @@ class AttnMetadata:
     # share leading pages and take the shared-prefix kernel (opt-in, see
     # ops.shared_prefix_plan); None = the per-row decode kernel
     decode_shared: Optional[tuple] = None
+    # a GraphRunner decode step: one row per sequence, slot_mapping[b] the
+    # slot of token decode_ctx_lens[b] - 1, padded rows at ctx 0 / slot -1.
+    # What ops.fused_rope_attn_ready needs to fold the KV append into the
+    # decode attention kernel.
+    decode_step: bool = False
     # prefill part
     num_prefill_tokens: int = 0
     prefill_page_table: Optional[torch.Tensor] = None  # [Bp, maxp] int32
@@ -238,6 +243,32 @@ class Attention(torch.nn.Module):
         qkv = linear_lora(x, self.wqkv, self.lora, "qkv")
         if meta.lora_slots is not None:
             lora_bank_delta_(qkv, x, self.lora_bank["qkv"], meta)
+        if ops.fused_rope_attn_ready(
+                self.hq, self.hkv, self.hd, kcache.shape[2], meta.v_transposed,
+                kcache.dtype, decode_step=meta.decode_step, num_tokens=T,
+                num_decode=meta.num_decode,
+                shared_prefix=meta.decode_shared is not None,
+                on_gpu=qkv.is_cuda):
+            # the decode kernel ropes q and appends k/v itself: no
+            # rope_append_qkv launch, no q buffer
+            out = ops.paged_attention_decode_rope(
+                qkv, self.bqkv, meta.positions, meta.slot_mapping, cos_sin,
+                kcache, vcache, meta.decode_page_table, meta.decode_ctx_lens,
+                self.scale, meta.decode_scratch, self.hq, self.hkv, self.hd)
+        else:
+            out = self._rope_append_attend(qkv, cos_sin, kcache, vcache, meta)
+        out = out.view(T, self.hq * self.hd)
+        o = linear_lora(out, self.wo, self.lora, "o")
+        if meta.lora_slots is not None:
+            # row-parallel: the partial deltas sum in the all-reduce below
+            lora_bank_delta_(o, out, self.lora_bank["o"], meta)
+        return self.tp.all_reduce(o)
+
+    def _rope_append_attend(self, qkv, cos_sin, kcache, vcache,
+                            meta: AttnMetadata):
+        """rope_append_qkv, then the attention kernel of each part of the
+        step; [T, Hq, hd]."""
+        T = qkv.shape[0]
         # fused epilogue: strided qkv read (+bias) -> rope -> q contiguous,
         # k/v scattered into the cache (one kernel vs four)
         q = ops.rope_append_qkv(qkv, self.bqkv, meta.positions,
@@ -268,12 +299,7 @@ class Attention(torch.nn.Module):
                 qh[nd:].contiguous(), kcache, vcache, meta.prefill_page_table,
                 meta.seq_q_start, meta.seq_q_len, meta.seq_ctx_len, self.scale,
                 meta.prefill_tiles, v_transposed=meta.v_transposed)
-        out = out.view(T, self.hq * self.hd)
-        o = linear_lora(out, self.wo, self.lora, "o")
-        if meta.lora_slots is not None:
-            # row-parallel: the partial deltas sum in the all-reduce below
-            lora_bank_delta_(o, out, self.lora_bank["o"], meta)
-        return self.tp.all_reduce(o)
+        return out
 
 
 class SwiGLUMLP(torch.nn.Module):

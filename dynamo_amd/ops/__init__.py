@@ -679,6 +679,85 @@ def paged_attention_decode(q, kcache, vcache, page_table, ctx_lens, scale,
     return r
 
 
+# --------------------------------------------------------------------------
+# Rope + KV append inside decode attention (paged_decode_mfma_swapped_dmajor_
+# rope, csrc/attention_decode_impl.h): a decode step's rope_append_qkv launch
+# folded into phase 1 of the d-major decode kernel, equal bits in the output
+# and in both caches. DYNAMO_FUSED_ROPE_ATTN / set_fused_rope_attn switch it;
+# off, and wherever fused_rope_attn_ready says no, the two kernels run.
+FUSED_ROPE_ATTN_DEFAULT = True
+
+_fused_rope_attn_override: "bool | None" = None
+
+
+def set_fused_rope_attn(on: "bool | None") -> None:
+    """In-process override of DYNAMO_FUSED_ROPE_ATTN (None = follow the
+    env). A captured decode graph keeps the route it was captured with."""
+    global _fused_rope_attn_override
+    _fused_rope_attn_override = on
+
+
+def fused_rope_attn_enabled() -> bool:
+    if _fused_rope_attn_override is not None:
+        return _fused_rope_attn_override
+    from dynamo_amd import envs
+    return envs.get("DYNAMO_FUSED_ROPE_ATTN", FUSED_ROPE_ATTN_DEFAULT, bool)
+
+
+def fused_rope_attn_ready(Hq: int, Hkv: int, head_dim: int, page_size: int,
+                          v_transposed: bool, kv_dtype, *, decode_step: bool,
+                          num_tokens: int, num_decode: int,
+                          shared_prefix: bool = False,
+                          on_gpu: bool = True) -> bool:
+    """Does this attention call take the fused kernel? Only a pure decode
+    step of the engine's persistent-buffer path (decode_step: one row per
+    sequence, slot_mapping[b] the slot of token ctx_lens[b] - 1, padded rows
+    at slot -1) over bf16 d-major V pages with a GQA group the d-major kernel
+    serves. fp8 KV, token-major V, prefill and mixed steps, multi-query,
+    shared-prefix and the CPU path keep rope_append_qkv + the attention
+    kernels."""
+    if not (on_gpu and decode_step and fused_rope_attn_enabled()):
+        return False
+    if shared_prefix or num_decode <= 0 or num_tokens != num_decode:
+        return False
+    if Hkv <= 0 or Hq % Hkv:
+        return False
+    return (v_transposed and kv_dtype == torch.bfloat16
+            and 2 <= Hq // Hkv <= 16 and head_dim == 128
+            and page_size % 32 == 0 and page_size & (page_size - 1) == 0)
+
+
+def paged_attention_decode_rope(qkv, bias, positions, slot_mapping, cos_sin,
+                                kcache, vcache, page_table, ctx_lens, scale,
+                                scratch: "DecodeScratch | None",
+                                num_q_heads: int, num_kv_heads: int,
+                                head_dim: int, out=None, nt_policy: int = -1):
+    """rope_append_qkv(v_transposed=True) followed by
+    paged_attention_decode(v_transposed=True) for one decode step, qkv
+    [B, (Hq + 2 Hkv) * hd] -> [B, Hq, hd]; the new token's k and v land in
+    the caches. On the GPU one phase-1 kernel does both (bf16 d-major V
+    pages); slot_mapping[b] must be the slot of token ctx_lens[b] - 1 under
+    page_table[b], or negative for a row that appends nothing."""
+    B = qkv.shape[0]
+    if qkv.is_cuda:
+        if out is None:
+            out = torch.empty(B, num_q_heads, head_dim, dtype=qkv.dtype,
+                              device=qkv.device)
+        assert scratch is not None, "GPU decode needs a DecodeScratch"
+        partial, ml = scratch.view(B)
+        hip().paged_attention_decode_rope(
+            out, qkv, bias, positions, slot_mapping, cos_sin, kcache, vcache,
+            page_table, ctx_lens, partial, ml, scale, scratch.chunk_tokens,
+            nt_policy)
+        return out
+    q = rope_append_qkv(qkv, bias, positions, slot_mapping, cos_sin, kcache,
+                        vcache, num_q_heads, num_kv_heads, head_dim,
+                        v_transposed=True)
+    return paged_attention_decode(q.view(B, num_q_heads, head_dim), kcache,
+                                  vcache, page_table, ctx_lens, scale,
+                                  scratch, out=out, v_transposed=True)
+
+
 def prefill_tile_rows(num_q_heads: int, num_kv_heads: int) -> int:
     """Q-tile granularity of the native prefill kernel: the 8-wave 32x32
     kernel handles GQA groups G in {2,4,8} with (8/G)*32-row tiles; the
