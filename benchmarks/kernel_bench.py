@@ -315,6 +315,69 @@ def bench_sampling(B=16, V=128256):
         print(f"topkp_sample [B{B} V{V}] {name:5s}: {row}")
 
 
+def bench_logprobs(V=128256, Bs=(1, 16, 64), Ns=(1, 5, 20), rounds=3,
+                   calls=200):
+    """ops.top_logprobs (csrc/logprobs.hip) against the torch sequence of
+    compute_logprobs (log_softmax, topk, gather) on the same fp32 logits.
+    cold: call i reads copy i % R of the rows, R copies together past 640 MB
+    (the Infinity Cache holds 256 MB); warm: the same rows every call, as
+    right after the sampler has read them. Device events around `calls`
+    back-to-back eager calls, the two alternated `rounds` times, best of the
+    rounds. Then the kernel at every power-of-two slices per row next to the
+    dispatch's own choice (ops._logprobs_slices), cold, N = 20."""
+    def event_time(fn):
+        start, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        for i in range(5):
+            fn(i)
+        start.record()
+        for i in range(calls):
+            fn(i)
+        end.record()
+        end.synchronize()
+        return start.elapsed_time(end) * 1e-3 / calls
+
+    for B in Bs:
+        R = -(-640_000_000 // (B * V * 4))
+        pool = torch.randn(R * B, V, device="cuda")
+        sampled = torch.randint(0, V, (B,), dtype=torch.int32, device="cuda")
+        idx = sampled.long().unsqueeze(-1)
+
+        def rows(i, cold):
+            r = i % R if cold else 0
+            return pool[r * B:(r + 1) * B]
+
+        for N in Ns:
+            want = torch.full((B,), N, dtype=torch.int32, device="cuda")
+            out = ops.top_logprobs(rows(0, False), sampled, want, N)
+
+            def old(i, cold):
+                lp = torch.log_softmax(rows(i, cold), dim=-1)
+                torch.topk(lp, N, dim=-1)
+                lp.gather(-1, idx)
+
+            def new(i, cold, S=None):
+                ops.top_logprobs(rows(i, cold), sampled, want, N, out, S)
+
+            for cold in (True, False):
+                ts = {"torch": [], "kernel": []}
+                for _ in range(rounds):
+                    ts["torch"].append(event_time(lambda i: old(i, cold)))
+                    ts["kernel"].append(event_time(lambda i: new(i, cold)))
+                t, k = min(ts["torch"]), min(ts["kernel"])
+                print(f"logprobs [B{B} V{V} N{N}] {'cold' if cold else 'warm'}"
+                      f": torch {t*1e6:7.1f} us | kernel {k*1e6:7.1f} us "
+                      f"{B*V*4/k/1e9:7.1f} GB/s | {t/k:5.2f}x")
+        pick = ops._logprobs_slices(B, V)
+        sweep = sorted({1, 2, 4, 8, 16, 32, 64, pick})
+        ts = {S: [] for S in sweep}
+        for _ in range(rounds):
+            for S in sweep:
+                ts[S].append(event_time(lambda i: new(i, True, S)))
+        print(f"logprobs [B{B} V{V} N{Ns[-1]}] cold, slices (dispatch {pick}): "
+              + " | ".join(f"{S} {min(v)*1e6:6.1f} us" for S, v in ts.items()))
+        del pool
+
+
 def timeit_graph(fn, n=100, reps=20):
     """Per-call time of a latency-bound kernel as the decode graph runs it:
     n dependent calls captured into one hipGraph, so the figure is kernel +
@@ -1082,6 +1145,8 @@ if __name__ == "__main__":
     if w in ("all", "logits"):
         bench_logit_processors(B=16)
         bench_logit_processors(B=64)
+    if w in ("all", "logprobs"):
+        bench_logprobs()
     if w in ("all", "gemm"):
         bench_gemm()
         bench_gemm(M=8192)

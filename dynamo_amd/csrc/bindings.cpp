@@ -82,6 +82,12 @@ void logits_process(torch::Tensor logits, c10::optional<torch::Tensor> counts,
                     c10::optional<torch::Tensor> bias_off,
                     c10::optional<torch::Tensor> bias_ids,
                     c10::optional<torch::Tensor> bias_vals, bool allow_fast);
+// logprobs.hip
+void top_logprobs(torch::Tensor token_lp, torch::Tensor top_lp,
+                  torch::Tensor top_ids, torch::Tensor logits,
+                  torch::Tensor sampled, torch::Tensor want,
+                  torch::Tensor stats, torch::Tensor cand, int64_t nmax,
+                  int64_t slices);
 // skinny_gemm.hip
 void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                  int64_t wpb, int64_t u, int64_t nt, bool nontemporal,
@@ -268,6 +274,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("counts"), py::arg("slot"), py::arg("params"),
         py::arg("bias_off") = py::none(), py::arg("bias_ids") = py::none(),
         py::arg("bias_vals") = py::none(), py::arg("allow_fast") = true);
+  // logprob of sampled[b] and the top min(want[b], V) (id, logprob) of row b
+  // of fp32 logits [B, V], lowest id first among equal logits; want[b] == 0
+  // skips the row, slots past want[b] are not written. 1 <= nmax <= 20;
+  // stats fp32 [B, slices, 2] and cand int64 [B, slices, nmax] are scratch
+  m.def("top_logprobs", &top_logprobs, py::arg("token_lp"), py::arg("top_lp"),
+        py::arg("top_ids"), py::arg("logits"), py::arg("sampled"),
+        py::arg("want"), py::arg("stats"), py::arg("cand"), py::arg("nmax"),
+        py::arg("slices"));
   // y = x @ w^T for 1 <= M <= 16 (decode); raises on anything the kernel
   // does not handle - dispatch and fallback live in ops.linear. glu = true
   // on any of the three GEMMs: w is a gate/up weight [2I, K], y is [M, I] =

@@ -48,6 +48,10 @@ def compute_logprobs(logits: torch.Tensor, sampled: torch.Tensor,
     want = [r.sampling.logprobs for r in reqs]
     if not any(want):
         return [None] * len(reqs)
+    if (ops.logprobs_kernel_enabled() and logits.is_cuda
+            and logits.dtype == torch.float32 and logits.is_contiguous()
+            and max(want) <= ops.LOGPROBS_MAX_N):
+        return _kernel_logprobs(logits, sampled, want)
     lp = torch.log_softmax(logits.float(), dim=-1)
     kmax = min(max(want), lp.shape[-1])
     topv, topi = torch.topk(lp, kmax, dim=-1)
@@ -62,6 +66,29 @@ def compute_logprobs(logits: torch.Tensor, sampled: torch.Tensor,
                     "top": [[topi_l[i][j], topv_l[i][j]]
                             for j in range(min(n, kmax))]})
     return out
+
+
+def _kernel_logprobs(logits: torch.Tensor, sampled: torch.Tensor, want):
+    """compute_logprobs on the fused kernel (ops.top_logprobs): one small
+    host-to-device tensor, one launch pair, and one device-to-host copy of the
+    three outputs, which share a flat fp32 buffer (the ids as its int32
+    tail). Rows with want == 0 are skipped by the kernel."""
+    B, V = logits.shape
+    nmax = max(want)
+    dev = logits.device
+    buf = torch.empty(B * (1 + 2 * nmax), dtype=torch.float32, device=dev)
+    out = (buf[:B], buf[B:B + B * nmax].view(B, nmax),
+           buf[B + B * nmax:].view(torch.int32).view(B, nmax))
+    ops.top_logprobs(logits, sampled.to(torch.int32).contiguous(),
+                     torch.tensor(want, dtype=torch.int32).to(dev), nmax, out)
+    host = buf.cpu()
+    own_l = host[:B].tolist()
+    topv_l = host[B:B + B * nmax].view(B, nmax).tolist()
+    topi_l = host[B + B * nmax:].view(torch.int32).view(B, nmax).tolist()
+    return [None if not n else
+            {"token_logprob": own_l[i],
+             "top": [[topi_l[i][j], topv_l[i][j]] for j in range(min(n, V))]}
+            for i, n in enumerate(want)]
 
 
 _GOLDEN = 0x9E3779B97F4A7C15

@@ -71,6 +71,12 @@ ENV_VARS = {
         "once per group of up to 64 / G rows; a step without such a group "
         "runs the decode kernel as before (d-major V pages, head_dim 128). "
         "Default: off",
+    "DYNAMO_LOGPROBS_KERNEL":
+        "1 = requests with logprobs (at most ops.LOGPROBS_MAX_N per token) "
+        "get them from the fused kernel (csrc/logprobs.hip: one pass over "
+        "the fp32 logits row, no [B, V] temporary, lowest id first among "
+        "equal logits) instead of torch log_softmax + topk + gather. Values "
+        "differ from the torch path by fp32 rounding. Default: off",
     "DYNAMO_MAX_LORAS":
         "default of the worker's --max-loras: adapter-bank slots for "
         "per-request LoRA (default 0 = engine-level activation only)",

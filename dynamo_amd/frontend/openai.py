@@ -88,6 +88,10 @@ class ChatRequest(BaseModel):
     stop: Optional[Union[str, List[str]]] = None
     seed: int = 0
     ignore_eos: bool = False
+    # OpenAI chat logprobs: the sampled token's logprob per output token and,
+    # with top_logprobs = N (0-20), the N most likely tokens beside it
+    logprobs: bool = False
+    top_logprobs: Optional[int] = None
     # logit processors (SamplingParams): None = the request template's value,
     # else neutral. logit_bias maps token ids (JSON: strings) to [-100, 100]
     repetition_penalty: Optional[float] = None
@@ -167,6 +171,18 @@ def check_penalties(p: dict, vocab_size: Optional[int]):
         if not -100.0 <= v <= 100.0:
             bad("logit_bias", f"value for {k!r} must be in [-100, 100], "
                               f"got {v}")
+
+
+MAX_TOP_LOGPROBS = 20
+
+
+def _logprobs_of(req) -> int:
+    """SamplingParams.logprobs of a request: the completions route's integer,
+    or for chat max(1, top_logprobs) when `logprobs` is true."""
+    lp = getattr(req, "logprobs", None)
+    if isinstance(lp, bool):
+        return max(1, getattr(req, "top_logprobs", None) or 0) if lp else 0
+    return lp or 0
 
 
 def _session_of(req, raw: Request) -> Optional[str]:
@@ -260,7 +276,7 @@ def build_app(manager: ModelManager,
         sampling = {"temperature": _temp_of(req), "top_p": req.top_p,
                     "top_k": getattr(req, "top_k", 0),
                     "seed": getattr(req, "seed", 0),
-                    "logprobs": getattr(req, "logprobs", None) or 0}
+                    "logprobs": _logprobs_of(req)}
         sampling.update(_penalties_of(req))
         # checkpoint generation_config eos ids (possibly several, e.g.
         # llama-3) win over the tokenizer's probed eos token
@@ -956,6 +972,14 @@ def build_app(manager: ModelManager,
     async def chat(req: ChatRequest, raw: Request):
         entry = _entry_or_404(_model_of(req))
         _check_penalties(entry, req)
+        if req.top_logprobs is not None:
+            if not 0 <= req.top_logprobs <= MAX_TOP_LOGPROBS:
+                raise HTTPException(
+                    400, f"top_logprobs: must be in [0, {MAX_TOP_LOGPROBS}], "
+                         f"got {req.top_logprobs}")
+            if req.top_logprobs and not req.logprobs:
+                raise HTTPException(
+                    400, "top_logprobs: needs logprobs to be true")
         REQS.labels(entry.name, "chat").inc()
         mm_extra = None
         mm = await _mm_prepare(entry, req)
@@ -1034,6 +1058,7 @@ def build_app(manager: ModelManager,
             return StreamingResponse(sse(), media_type="text/event-stream")
 
         produced: List[int] = []
+        lps: List[dict] = []
         finish = None
         stops = _stop_list(req)
         text_cut = None
@@ -1041,6 +1066,7 @@ def build_app(manager: ModelManager,
         async for chunk in _run(entry, token_ids, req, rid, _session_of(req, raw), extra=mm_extra):
             prev = len(produced)
             produced.extend(chunk.get("token_ids", []))
+            lps.extend(chunk.get("logprobs", []))
             finish = chunk.get("finish_reason") or finish
             if stops:
                 acc += entry.tokenizer.decode_incremental(produced, prev)
@@ -1068,10 +1094,20 @@ def build_app(manager: ModelManager,
             asyncio.get_running_loop().create_task(_spec_prefill(
                 entry, [m.model_dump() for m in req.messages],
                 text_out or ""))
+        logprobs_out = None
+        if req.logprobs and lps:
+            tok = entry.tokenizer
+            ntop = req.top_logprobs or 0
+            logprobs_out = {"content": [
+                {"token": tok.decode([t]), "logprob": d["token_logprob"],
+                 "top_logprobs": [{"token": tok.decode([i]), "logprob": v}
+                                  for i, v in d["top"][:ntop]]}
+                for t, d in zip(produced, lps)]}
         return {
             "id": rid, "object": "chat.completion", "created": int(t0),
             "model": entry.name,
             "choices": [{"index": 0, "message": message,
+                "logprobs": logprobs_out,
                 "finish_reason": ("tool_calls" if tool_calls
                                   else finish or "stop")}],
             "usage": {"prompt_tokens": len(token_ids),

@@ -1068,6 +1068,63 @@ def topkp_sample(logits: torch.Tensor, inv_temp: torch.Tensor,
     return out
 
 
+# --------------------------------------------------------------------------
+# Fused top-N logprobs (csrc/logprobs.hip; the semantics are written out at
+# torch_ref.top_logprobs). Opt-in: values differ from torch.log_softmax by
+# fp32 rounding and ties are ordered (lowest id first) where torch.topk
+# leaves them unspecified.
+LOGPROBS_MAX_N = 20           # the OpenAI top_logprobs ceiling
+_LOGPROBS_MAX_SLICES = 64     # kMaxSlices of the kernel
+
+_logprobs_kernel_override: "bool | None" = None
+
+
+def set_logprobs_kernel(on: "bool | None") -> None:
+    """In-process override of DYNAMO_LOGPROBS_KERNEL (None = follow the
+    env)."""
+    global _logprobs_kernel_override
+    _logprobs_kernel_override = on
+
+
+def logprobs_kernel_enabled() -> bool:
+    if _logprobs_kernel_override is not None:
+        return _logprobs_kernel_override
+    from dynamo_amd import envs
+    return envs.get("DYNAMO_LOGPROBS_KERNEL", False, bool)
+
+
+def _logprobs_slices(B: int, V: int) -> int:
+    """Slices per row of the kernel's first phase: two blocks per CU over the
+    batch, no slice under 2048 tokens (one block-wide step of 16-byte loads).
+    profiles/README.md, "Fused logprobs"."""
+    return max(1, min(_LOGPROBS_MAX_SLICES, -(-512 // max(B, 1)), V // 2048))
+
+
+def top_logprobs(logits: torch.Tensor, sampled: torch.Tensor,
+                 want: torch.Tensor, nmax: int, out=None, slices=None):
+    """(token_lp [B] fp32, top_lp [B, nmax] fp32, top_ids [B, nmax] int32) of
+    contiguous fp32 logits [B, V]: the logprob of sampled[b] and the top
+    min(want[b], V) entries of row b, larger logit first and lower id first
+    among equal logits. want[b] == 0 skips the row; slots past want[b] keep
+    what `out` (the three tensors, else fresh uninitialised ones) held.
+    sampled and want are int32 [B]; 1 <= nmax <= LOGPROBS_MAX_N. `slices`
+    overrides the kernel's slices per row (benchmarks)."""
+    if not 1 <= nmax <= LOGPROBS_MAX_N:
+        raise ValueError(f"nmax {nmax} outside [1, {LOGPROBS_MAX_N}]")
+    if not logits.is_cuda:
+        return torch_ref.top_logprobs(logits, sampled, want, nmax, out)
+    B, V = logits.shape
+    if out is None:
+        out = (torch.empty(B, dtype=torch.float32, device=logits.device),
+               torch.empty(B, nmax, dtype=torch.float32, device=logits.device),
+               torch.empty(B, nmax, dtype=torch.int32, device=logits.device))
+    S = slices or _logprobs_slices(B, V)
+    stats = torch.empty(B, S, 2, dtype=torch.float32, device=logits.device)
+    cand = torch.empty(B, S, nmax, dtype=torch.int64, device=logits.device)
+    hip().top_logprobs(*out, logits, sampled, want, stats, cand, nmax, S)
+    return out
+
+
 def topk_gating(logits: torch.Tensor, k: int):
     """softmax + renormalized top-k over experts. logits [T, E] fp32."""
     if logits.is_cuda:

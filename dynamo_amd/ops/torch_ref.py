@@ -216,6 +216,35 @@ def topkp_keep_mask(logits: torch.Tensor, top_k, top_p) -> torch.Tensor:
     return mask
 
 
+def top_logprobs(logits, sampled, want, nmax, out=None):
+    """The contract of csrc/logprobs.hip, computed in float64 and returned as
+    (token_lp [B] fp32, top_lp [B, nmax] fp32, top_ids [B, nmax] int32).
+
+    For row b with n = min(want[b], V) > 0: token_lp[b] is the log-softmax of
+    the row at sampled[b], and slots 0..n-1 of top_* hold the n largest
+    entries, larger logit first and lower token id first among equal logits
+    (a stable descending sort; -inf entries come last with logprob -inf).
+    Slots >= n and rows with want[b] == 0 keep what `out` held (zeros if
+    None)."""
+    B, V = logits.shape
+    if out is None:
+        out = (torch.zeros(B, dtype=torch.float32),
+               torch.zeros(B, nmax, dtype=torch.float32),
+               torch.zeros(B, nmax, dtype=torch.int32))
+    token_lp, top_lp, top_ids = out
+    x = logits.detach().cpu().double()
+    lp = torch.log_softmax(x, dim=-1)
+    _, idx = torch.sort(x, dim=-1, descending=True, stable=True)
+    for b, (w, s) in enumerate(zip(want.tolist(), sampled.tolist())):
+        n = min(w, V, nmax)
+        if n <= 0:
+            continue
+        token_lp[b] = lp[b, s]
+        top_ids[b, :n] = idx[b, :n]
+        top_lp[b, :n] = lp[b, idx[b, :n]]
+    return out
+
+
 # --------------------------------------------------------------------------
 # batched LoRA: every row picks its adapter from a bank by slot
 def lora_shrink(t, x, A_bank, slots, ranks):

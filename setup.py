@@ -32,6 +32,7 @@ hip_sources = [
         "mx_gemm.hip",
         "sampling.hip",
         "logits_process.hip",
+        "logprobs.hip",
         "moe.hip",
         "moe_decode.hip",
         "moe_tile_gemm.hip",
